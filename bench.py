@@ -95,6 +95,32 @@ def _alloc(pt, shape, dtype, pin):
     return np.empty(shape, dtype)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240531
+
+
+def dump_outputs(dirpath, outputs):
+    """--dump-outputs: write each named array as DIR/<name>.npy (float64).
+    Arrays are indexed along axis 0; one whose share of the 64 MB budget
+    is exceeded is reduced to a fixed, seeded sample of its rows (sorted
+    row indices, the same for every run with the same shapes), so two
+    builds run with the same arguments can be compared file by file."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        row_bytes = 8 * max(int(np.prod(a.shape[1:])), 1)
+        keep = cap // row_bytes
+        if a.shape[0] > keep:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            rows = np.sort(rng.choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirpath, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_partitioned_stateful(args, mesh, cells, rank, world, local, device):
     """BASELINE config 3 (default partitioned mode): Morton element
     partition across ranks, ghost rings, cross-rank handoff over RCCL,
@@ -163,6 +189,9 @@ def run_partitioned_stateful(args, mesh, cells, rank, world, local, device):
 
     global_flux = pe.flux_global()
     st = pe.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {"flux": np.asarray(global_flux).reshape(-1)})
     if args.write_vtk and rank == 0:
         f = np.asarray(global_flux)
         if args.ngroups > 1:
@@ -254,6 +283,9 @@ def run_partitioned(args, mesh, cells, rank, world, local, device):
         elapsed = elapsed_local
 
     global_flux = ptal.flux_global()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     {"flux": np.asarray(global_flux).reshape(-1)})
     if args.write_vtk:
         ptal.write_tally_results(args.write_vtk)
     if rank == 0:
@@ -336,7 +368,20 @@ def main():
                          "rcclComm over xGMI / TCP on CPU) instead of "
                          "torch.distributed; same metric, config notes the "
                          "stack")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path "
+                         "computed (flux tally; in replicated mode also the "
+                         "committed positions and element ids) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all "
+                         "(larger arrays: a fixed seeded row sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure; the benchmark has none today (a "
+                         "plain run only sets up, warms up, times --steps "
+                         "steps and reports), so this currently adds nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
 
@@ -447,6 +492,14 @@ def main():
     # flux all-reduce + optional write (outside timed region, parity with
     # the reference's single reduction at WriteTallyResults)
     global_flux = comm.sum_array(eng.flux())
+    if args.dump_outputs and rank == 0:
+        # what a caller of move() reads back: the tally plus the committed
+        # particle state (rank 0's own particles in a multi-rank run)
+        dump_outputs(args.dump_outputs, {
+            "flux": np.asarray(global_flux).reshape(-1),
+            "positions": np.asarray(eng.positions()).reshape(-1, 3),
+            "elem_ids": np.asarray(eng.elem_ids()).reshape(-1),
+        })
     if args.write_vtk and rank == 0:
         pt.write_tally_vtk(args.write_vtk, mesh, global_flux)
 

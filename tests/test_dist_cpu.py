@@ -106,6 +106,77 @@ def test_bench_single_process_cpu(tmp_path):
     assert r["config"]["lost_particles"] == 0
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files of what the timed path
+    computed; same arguments -> same inputs -> same outputs (flux to fp64
+    reassociation noise, committed particle state exactly); --full is
+    accepted and leaves the headline contract intact."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--particles", "2000",
+             "--mesh-tets", "3000", "--device", "cpu",
+             "--dump-outputs", str(d)] + extra,
+            capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr
+        r = json.loads(out.stdout.strip().splitlines()[-1])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        arrs = {k: np.load(d / f"{k}.npy")
+                for k in ("flux", "positions", "elem_ids")}
+        assert sorted(p.name for p in d.iterdir()) == [
+            "elem_ids.npy", "flux.npy", "positions.npy"]
+        for a in arrs.values():
+            assert a.dtype == np.float64
+        assert arrs["flux"].shape == (r["config"]["mesh_tets"],)
+        assert arrs["positions"].shape == (2000, 3)
+        assert arrs["elem_ids"].shape == (2000,)
+        assert abs(arrs["flux"].sum() - r["config"]["flux_sum"]) \
+            <= 1e-12 * abs(r["config"]["flux_sum"])
+        dumps.append(arrs)
+    np.testing.assert_allclose(dumps[0]["flux"], dumps[1]["flux"],
+                               rtol=1e-12, atol=0)
+    assert np.array_equal(dumps[0]["positions"], dumps[1]["positions"])
+    assert np.array_equal(dumps[0]["elem_ids"], dumps[1]["elem_ids"])
+
+
+def test_bench_dump_outputs_sampling(tmp_path, monkeypatch):
+    """Outputs over the size budget are cut to a fixed seeded row sample:
+    identical rows on every call, total size within the budget."""
+    import importlib.util
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location(
+        "_bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4800)
+    big = np.arange(3000, dtype=np.float64).reshape(1000, 3)
+    small = np.arange(7, dtype=np.int32)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"big": big, "small": small})
+    a = np.load(tmp_path / "a" / "big.npy")
+    b = np.load(tmp_path / "b" / "big.npy")
+    assert a.shape == (100, 3) and np.array_equal(a, b)
+    # rows are genuine rows of the source, in ascending order, no repeats
+    assert np.array_equal(a, big[(a[:, 0] / 3).astype(int)])
+    assert (np.diff(a[:, 0]) > 0).all()
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert a.nbytes + s.nbytes <= 4800
+
+
 def test_bench_gloo_world2(tmp_path):
     """bench.py under torchrun-style env (world 2, gloo): the exact launch
     contract the driver's SCALE run uses, minus the GPUs."""

@@ -279,7 +279,7 @@ def test_immediate_move_after_localization():
     assert e.stats()["lost_particles"] == 0
 
 
-def test_fp32_traversal_flux_agreement():
+def test_fp32_traversal_flux_agreement(tmp_path):
     """PUMITALLY_WALK=fp32 vs fp64: totals identical (both tally in fp64),
     per-element flux within sliver tolerance (fp32 only picks exit faces)."""
     import subprocess
@@ -296,16 +296,17 @@ def test_fp32_traversal_flux_agreement():
         "e = pt.TallyEngine(m, n, device='cpu')\n"
         "e.copy_initial_position(o.ravel())\n"
         "e.move(o.ravel(), d.ravel(), np.ones(n, np.int8), w)\n"
-        "np.save('/tmp/fp_flux_' + __import__('os').environ['PUMITALLY_WALK'], e.flux())\n"
+        "np.save('fp_flux_' + __import__('os').environ['PUMITALLY_WALK'], e.flux())\n"
     )
     repo = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
     for mode in ("fp64", "fp32"):
         env = dict(_os.environ, PUMITALLY_WALK=mode, PYTHONPATH=repo)
         r = subprocess.run([sys.executable, "-c", code], env=env,
+                           cwd=str(tmp_path),
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
-    f64 = np.load("/tmp/fp_flux_fp64.npy")
-    f32 = np.load("/tmp/fp_flux_fp32.npy")
+    f64 = np.load(tmp_path / "fp_flux_fp64.npy")
+    f32 = np.load(tmp_path / "fp_flux_fp32.npy")
     assert abs(f64.sum() - f32.sum()) < 1e-9 * f64.sum()
     # per-element: identical up to rare near-tie face-order slivers
     scale = np.abs(f64).max()
