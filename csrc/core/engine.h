@@ -50,6 +50,16 @@ struct EngineStats {
   // retry in grid_locate / Mesh::locate).  A nonzero count near partition
   // cuts can mean mis-assigned particles; surfaced so it is never silent.
   int64_t loose_localizations = 0;
+  // Origin elision (GPU engine, Engine::origin_elide): particles whose
+  // origin was taken from the previous move's destinations already in
+  // device memory instead of being uploaded, and the origin bytes that did
+  // cross the link (24 per uploaded particle).  Cumulative; the CPU engine
+  // stages nothing and reports 0 for both.
+  int64_t origins_elided = 0;
+  int64_t origin_bytes_uploaded = 0;
+  // Host time spent in the elision compare pass (seeding copies included),
+  // cumulative seconds: what the feature costs the calling thread.
+  double origin_pass_seconds = 0.0;
 };
 
 // First-K lost-particle capture (walks that hit max_steps): enough to find
@@ -228,11 +238,40 @@ public:
   // PUMITALLY_WALK=fp32|fp64; both engines honor it so CPU remains the
   // bitwise oracle for the GPU in either mode.
   bool walk_fp32 = false;
+
+  // Origin elision (GPU engine's move(); see engine_gpu.hip): skip the
+  // upload of every origin that is bit-identical to the destination the
+  // previous move() staged, rebuilding it on device instead.  Results are
+  // unchanged; origin_elide=false restores the plain full upload.
+  // Env defaults: PUMITALLY_ORIGIN_ELIDE (0|1), PUMITALLY_ORIGIN_THREADS
+  // (host compare workers, capped at 16), PUMITALLY_ORIGIN_CHUNK (particles
+  // per host chunk; 0 = auto).  Per engine, so two engines in one process
+  // can differ.  The CPU engine ignores all three.
+  bool origin_elide = true;
+  int origin_threads = 8;
+  int64_t origin_chunk = 0;
 };
 
 inline bool default_walk_fp32() {
   const char *s = getenv("PUMITALLY_WALK");
   return s && std::string(s) == "fp32";
+}
+
+inline bool default_origin_elide() {
+  const char *s = getenv("PUMITALLY_ORIGIN_ELIDE");
+  return !s || atoi(s) != 0;
+}
+
+inline int default_origin_threads() {
+  const char *s = getenv("PUMITALLY_ORIGIN_THREADS");
+  const int k = s ? atoi(s) : 8;
+  return k < 1 ? 1 : (k > 16 ? 16 : k);
+}
+
+inline int64_t default_origin_chunk() {
+  const char *s = getenv("PUMITALLY_ORIGIN_CHUNK");
+  const int64_t c = s ? (int64_t)atoll(s) : 0;
+  return c < 0 ? 0 : c;
 }
 
 // Localization tolerance (accepted signed distance below a face plane),

@@ -25,7 +25,13 @@
 //     compute stream); buffer reuse is fenced with per-parity events.
 //     Pinned sources (pumiumtally_amd.pinned_array or app-registered
 //     buffers) run at full link rate.
+//   * That link is what bounds the host-staged step, so move() does not
+//     send what the device already has: origins that are bit for bit the
+//     previous move's destinations are rebuilt from the copy still in HBM
+//     (origin elision, see stage_elided below) -- 42 % fewer bytes per
+//     steady-state step, results unchanged.
 #include "../core/engine.h"
+#include "../core/origin_delta.h"
 #include "../core/walk.h"
 
 #include <hip/hip_runtime.h>
@@ -34,9 +40,11 @@
 #include <algorithm>
 #include <type_traits>
 #include <array>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -87,6 +95,38 @@ __global__ void k_iota(int32_t *__restrict__ a, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     a[i] = (int32_t)i;
+}
+
+// Origin elision, step 1: d_origin_[p] := the previous move's staged
+// destinations.  Plain streaming copy, 16 B per lane; `count` doubles.
+// Both buffers come straight from hipMalloc (256 B aligned).
+__global__ void k_copy_doubles(const double *__restrict__ src,
+                               double *__restrict__ dst, int64_t count) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t pairs = count / 2;
+  const double2 *__restrict__ s2 = reinterpret_cast<const double2 *>(src);
+  double2 *__restrict__ d2 = reinterpret_cast<double2 *>(dst);
+  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < pairs;
+       i += stride)
+    d2[i] = s2[i];
+  if ((count & 1) && blockIdx.x == 0 && threadIdx.x == 0)
+    dst[count - 1] = src[count - 1];
+}
+
+// Origin elision, step 2: overwrite the origins the host found changed.
+// idx holds caller particle indices in [0, n), strictly increasing, so no
+// two entries touch the same origin.
+__global__ void k_scatter_origins(const int32_t *__restrict__ idx,
+                                  const double *__restrict__ xyz,
+                                  double *__restrict__ origin, int64_t count) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = blockIdx.x * blockDim.x + threadIdx.x; j < count;
+       j += stride) {
+    const int64_t i = idx[j];
+    origin[i * 3] = xyz[j * 3];
+    origin[i * 3 + 1] = xyz[j * 3 + 1];
+    origin[i * 3 + 2] = xyz[j * 3 + 2];
+  }
 }
 
 __global__ void k_locate(const Plane *__restrict__ planes, GridView grid,
@@ -626,6 +666,9 @@ public:
     loc_tol_ = loc_tol_rel() * norm(mesh_.bbox_hi - mesh_.bbox_lo);
     walk_fp32 = default_walk_fp32();
     reflective = default_reflective();
+    origin_elide = default_origin_elide();
+    origin_threads = default_origin_threads();
+    origin_chunk = default_origin_chunk();
     const Vec3 c0 = mesh_.nelems > 0 ? mesh_.centroid(0) : Vec3{0, 0, 0};
     k_init_particles<<<grid_blocks(n_), kBlock, 0, s_comp_>>>(
         d_pos_, d_elem_, d_escaped_, d_s2c_, n_, c0.x, c0.y, c0.z);
@@ -654,6 +697,7 @@ public:
                     (void *)d_esc2_, (void *)d_s2c2_, d_sorttmp_})
       if (p) (void)hipFree(p);
     free_wr();
+    free_patch();
     for (auto &ev : copy_ev_) (void)hipEventDestroy(ev);
     for (auto &ev : kernels_done_) (void)hipEventDestroy(ev);
     (void)hipStreamDestroy(s_copy_);
@@ -694,16 +738,40 @@ public:
     // WAR fence: buffer set p was last read by the kernels of the move
     // two calls ago; its copies must wait for them.
     PT_HIP_CHECK(hipStreamWaitEvent(s_copy_, kernels_done_[p], 0));
-    if (origin)
-      stage(origin, n * 3 * sizeof(double), d_origin_[p], s_copy_);
-    stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
-    stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
-    stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
-    if (groups && d_groups_[p])
-      stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
-    if (responses) {
-      if (!d_resp_[p]) d_resp_[p] = dmalloc<double>(n_ * nscores);
-      stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+    if (responses && !d_resp_[p]) d_resp_[p] = dmalloc<double>(n_ * nscores);
+    // Origin elision applies when the host shadow holds exactly what the
+    // previous call staged into d_dest_[p^1]; every other case (continue
+    // semantics, switch off, back-off, first move) takes the plain upload.
+    const bool probe = origin && origin_elide && n > 0 && elide_skip_ == 0;
+    if (probe && shadow_valid_) {
+      stage_elided(p, origin, dest, flying, weights, groups, responses, n);
+    } else {
+      if (origin) {
+        stage(origin, n * 3 * sizeof(double), d_origin_[p], s_copy_);
+        stats_.origin_bytes_uploaded += n * 3 * (int64_t)sizeof(double);
+      }
+      stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
+      stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
+      stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
+      if (groups && d_groups_[p])
+        stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
+      if (responses)
+        stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+      // d_dest_[p] no longer matches the shadow (move_continue marks it
+      // invalid rather than paying for an update it may never use) ...
+      shadow_valid_ = false;
+      if (probe) {
+        // ... unless this is a full upload that seeds it: copy the
+        // caller's dest while the DMA engine is busy with the copies above.
+        ensure_elide_host(n);
+        const auto t0 = std::chrono::steady_clock::now();
+        origin_delta_seed(*delta_pool_, dest, shadow_.get(), 0, n,
+                          /*nontemporal=*/false);
+        stats_.origin_pass_seconds += seconds_since(t0);
+        shadow_valid_ = true;
+      } else if (origin && origin_elide && elide_skip_ > 0) {
+        --elide_skip_;
+      }
     }
     PT_HIP_CHECK(hipEventRecord(copy_ev_[p], s_copy_));
     PT_HIP_CHECK(hipStreamWaitEvent(s_comp_, copy_ev_[p], 0));
@@ -1035,6 +1103,186 @@ private:
     PT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
   }
 
+  // ---- origin elision ---------------------------------------------------
+  //
+  // The headline move() is bound by the host-to-device link, and 240 of its
+  // 570 MB are origins that, in steady state, are bit for bit the
+  // destinations the previous move() staged -- still in d_dest_[p^1].
+  // stage_elided() builds d_origin_[p] on device instead:
+  //   1. k_copy_doubles: d_origin_[p] := d_dest_[p^1]       (HBM only)
+  //   2. per host chunk, the origins the host delta pass found NOT
+  //      bit-identical to its shadow of the previous dest are uploaded as a
+  //      patch list and scattered over the copy (or, when more than half
+  //      of the chunk changed, the chunk's origins are uploaded whole).
+  // Every particle's 24 origin bytes in d_origin_[p] are therefore exactly
+  // the caller's: from the patch/whole upload, or from a device copy of a
+  // value the host proved bit-identical.  k_move is untouched and no
+  // particle state is consulted, so results cannot change.
+  //
+  // Ordering (everything below is enqueued on s_copy_, in this order,
+  // after move()'s wait on kernels_done_[p]):
+  //   * d_origin_[p] writers (copy kernel, scatters, whole-chunk uploads):
+  //     its last readers are the k_move launches of the move two calls
+  //     ago, which kernels_done_[p] covers -- the same fence the plain
+  //     origin upload relies on.  Scatter / whole-chunk upload follow the
+  //     copy kernel in stream order, so they overwrite it, never the
+  //     reverse; a scatter follows its own patch upload in stream order.
+  //   * d_dest_[p^1] reader (copy kernel): its writer is the previous
+  //     move's dest upload, earlier on s_copy_ (and complete: move() only
+  //     returns after hipStreamSynchronize(s_copy_)).  Its next writer is
+  //     the NEXT move's dest upload, later on s_copy_.  So the copy kernel
+  //     sees exactly the previous destinations.  This is why the copy runs
+  //     here and k_move never reads d_dest_[p^1] itself: the next move's
+  //     copies wait only for the kernels of two moves ago and would
+  //     overwrite the buffer under a k_move still reading it.
+  //   * patch buffers (d_patch_idx_/d_patch_xyz_, single set): written by
+  //     uploads and read by scatters on s_copy_ only, so stream order
+  //     serializes reuse across chunks and across moves.  The pinned host
+  //     side gives every chunk its own region, so workers filling chunk
+  //     c+1's patch never touch memory the DMA engine is still reading for
+  //     chunk c.
+  //   * s_comp_ waits on copy_ev_[p], recorded after all of the above.
+  //   * caller memory: the pass reads origin/dest synchronously; the
+  //     async copies that read caller memory are all on s_copy_, which
+  //     move() synchronizes before returning, as before.  The shadow is a
+  //     real copy, so the caller may scribble over dest right after.
+  // Validity: shadow_valid_ is only ever set by a move() that staged the
+  // shadow's contents into d_dest_[parity of that move]; the next move()
+  // has the opposite parity, so d_dest_[p^1] is that buffer.  The only
+  // writers of d_dest_ are move()/move_continue() (one code path); the
+  // plain path clears shadow_valid_.  move_device, copy_initial_position
+  // (stages into d_origin_[0] after a full sync), set_particle_state and
+  // the re-sort never touch d_dest_, and d_origin_[p] is rebuilt in full
+  // by every move that reads it.
+  static constexpr int kElideBackoffFirst = 16;
+  static constexpr int kElideBackoffMax = 256;
+
+  static double seconds_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() -
+                                         t0)
+        .count();
+  }
+
+  int64_t elide_chunk(int64_t n) const {
+    if (origin_chunk > 0) return std::max<int64_t>(origin_chunk, 64);
+    // Two chunks: the first half's patches upload while the second half is
+    // compared, and the whole-upload fallback is decided per half.  Every
+    // chunk costs one wake-up of the worker pool, bounded by its slowest
+    // thread; swept on MI355X, n/2 beat n/8 and n/32 (profiles/README.md).
+    return std::max<int64_t>((int64_t)262144, (n + 1) / 2);
+  }
+
+  void ensure_elide_host(int64_t n) {
+    const int want = origin_delta_clamp_threads(origin_threads);
+    if (!delta_pool_ || delta_pool_->nthreads() != want)
+      delta_pool_ = std::make_unique<OriginDeltaPool>(want);
+    if (!shadow_) shadow_.reset(new double[n * 3]);
+  }
+
+  void free_patch() {
+    if (h_patch_idx_) (void)hipHostFree(h_patch_idx_);
+    if (h_patch_xyz_) (void)hipHostFree(h_patch_xyz_);
+    if (d_patch_idx_) (void)hipFree(d_patch_idx_);
+    if (d_patch_xyz_) (void)hipFree(d_patch_xyz_);
+    h_patch_idx_ = d_patch_idx_ = nullptr;
+    h_patch_xyz_ = d_patch_xyz_ = nullptr;
+    patch_cap_ = 0;
+  }
+
+  void ensure_patch(int64_t need) {
+    if (need <= patch_cap_) return;
+    PT_HIP_CHECK(hipStreamSynchronize(s_copy_)); // scatters may still read
+    free_patch();
+    void *hi = nullptr, *hx = nullptr;
+    PT_HIP_CHECK(hipHostMalloc(&hi, need * sizeof(int32_t),
+                               hipHostMallocDefault));
+    h_patch_idx_ = (int32_t *)hi;
+    PT_HIP_CHECK(hipHostMalloc(&hx, need * 3 * sizeof(double),
+                               hipHostMallocDefault));
+    h_patch_xyz_ = (double *)hx;
+    d_patch_idx_ = dmalloc<int32_t>(need);
+    d_patch_xyz_ = dmalloc<double>(need * 3);
+    patch_cap_ = need;
+  }
+
+  void stage_elided(int p, const double *origin, const double *dest,
+                    const int8_t *flying, const double *weights,
+                    const uint16_t *groups, const double *responses,
+                    int64_t n) {
+    ensure_elide_host(n);
+    const int nthreads = delta_pool_->nthreads();
+    const int64_t chunk = elide_chunk(n);
+    int64_t need = 0;
+    for (int64_t lo = 0; lo < n; lo += chunk)
+      need += origin_delta_patch_capacity(std::min(chunk, n - lo), nthreads);
+    ensure_patch(need);
+    shadow_valid_ = false; // until every chunk's shadow has been refreshed
+    k_copy_doubles<<<grid_blocks(n * 3 / 2), kBlock, 0, s_copy_>>>(
+        d_dest_[p ^ 1], d_origin_[p], n * 3);
+    PT_HIP_CHECK(hipGetLastError());
+    // None of these depends on the host pass, so they go first and whole:
+    // the DMA engine has its ~330 MB queued before the first compare
+    // starts and the entire pass, first chunk included, runs in its shadow.
+    // (Measured on MI355X: interleaving per-chunk slices of these copies
+    // with the pass averaged 8.05 ms/step over a thread x chunk sweep,
+    // this order 7.05; profiles/README.md.)
+    stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
+    stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
+    stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
+    if (groups && d_groups_[p])
+      stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
+    if (responses)
+      stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+    int64_t region = 0, uploaded = 0;
+    for (int64_t lo = 0; lo < n; lo += chunk) {
+      const int64_t hi = std::min(n, lo + chunk);
+      const int64_t len = hi - lo;
+      const int64_t cap = origin_delta_patch_capacity(len, nthreads);
+      if (region + cap > patch_cap_)
+        throw std::runtime_error("origin elision: patch region overflow");
+      int32_t *hidx = h_patch_idx_ + region;
+      double *hxyz = h_patch_xyz_ + region * 3;
+      // Synchronous on the host; the copies enqueued above (and the
+      // patches of earlier chunks) keep the DMA engine busy meanwhile.
+      const auto t0 = std::chrono::steady_clock::now();
+      const OriginDeltaResult r = origin_delta_pass(
+          *delta_pool_, origin, dest, shadow_.get(), lo, hi, hidx, hxyz,
+          /*nontemporal=*/false);
+      stats_.origin_pass_seconds += seconds_since(t0);
+      if (r.overflow || r.changed * 2 > len) {
+        // a patch entry (28 B) costs more than the origin it replaces
+        stage(origin + lo * 3, len * 3 * sizeof(double),
+              d_origin_[p] + lo * 3, s_copy_);
+        uploaded += len;
+      } else if (r.changed > 0) {
+        origin_delta_compact(r, hidx, hxyz);
+        stage(hidx, r.changed * sizeof(int32_t), d_patch_idx_ + region,
+              s_copy_);
+        stage(hxyz, r.changed * 3 * sizeof(double),
+              d_patch_xyz_ + region * 3, s_copy_);
+        k_scatter_origins<<<grid_blocks(r.changed), kBlock, 0, s_copy_>>>(
+            d_patch_idx_ + region, d_patch_xyz_ + region * 3, d_origin_[p],
+            r.changed);
+        PT_HIP_CHECK(hipGetLastError());
+        uploaded += r.changed;
+      }
+      region += cap;
+    }
+    stats_.origins_elided += n - uploaded;
+    stats_.origin_bytes_uploaded += uploaded * 3 * (int64_t)sizeof(double);
+    shadow_valid_ = true;
+    // Adaptive back-off: a workload that resamples (nearly) everything
+    // gains nothing from the host pass.  Skip it for the next few moves
+    // (plain uploads, shadow left invalid), then seed and probe again,
+    // doubling the pause each time the probe fails.
+    if (uploaded * 2 > n) {
+      elide_skip_ = elide_backoff_;
+      elide_backoff_ = std::min(elide_backoff_ * 2, kElideBackoffMax);
+    } else {
+      elide_backoff_ = kElideBackoffFirst;
+    }
+  }
+
   template <bool F32, bool Scored, bool Periodic, bool Agg = false>
   void launch_move_one(const double *origin, const double *dest,
                        const int8_t *flying, const double *weights,
@@ -1136,6 +1384,19 @@ private:
   int64_t moves_since_sort_ = 0;
   uint64_t parity_ = 0;
   Vec3 sort_scale_{0, 0, 0};
+
+  // Origin elision (stage_elided): host shadow of the dest staged by the
+  // previous move() (3*n doubles, plain memory), compare workers, and the
+  // patch list (pinned host + device, patch_cap_ entries of int32 + 3
+  // doubles).  All allocated on first use.
+  std::unique_ptr<double[]> shadow_;
+  bool shadow_valid_ = false;
+  std::unique_ptr<OriginDeltaPool> delta_pool_;
+  int32_t *h_patch_idx_ = nullptr, *d_patch_idx_ = nullptr;
+  double *h_patch_xyz_ = nullptr, *d_patch_xyz_ = nullptr;
+  int64_t patch_cap_ = 0;
+  int elide_skip_ = 0;                     // plain moves left in a back-off
+  int elide_backoff_ = kElideBackoffFirst; // length of the next back-off
 
   hipStream_t s_copy_{}, s_comp_{};
   std::array<hipEvent_t, 2> copy_ev_{};

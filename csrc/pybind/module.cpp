@@ -679,6 +679,17 @@ PYBIND11_MODULE(_core, m) {
       .def_property(
           "max_steps", [](const PyEngine &e) { return e.eng->max_steps; },
           [](PyEngine &e, int v) { e.eng->max_steps = v; })
+      // origin elision settings (engine.h); per engine, GPU engine only
+      .def_property(
+          "origin_elide", [](const PyEngine &e) { return e.eng->origin_elide; },
+          [](PyEngine &e, bool v) { e.eng->origin_elide = v; })
+      .def_property(
+          "origin_threads",
+          [](const PyEngine &e) { return e.eng->origin_threads; },
+          [](PyEngine &e, int v) { e.eng->origin_threads = v; })
+      .def_property(
+          "origin_chunk", [](const PyEngine &e) { return e.eng->origin_chunk; },
+          [](PyEngine &e, int64_t v) { e.eng->origin_chunk = v; })
       .def("copy_initial_position",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> p) {
              if ((int64_t)p.size() != e.eng->num_particles() * 3)
@@ -925,6 +936,9 @@ PYBIND11_MODULE(_core, m) {
         d["moves"] = s.moves;
         d["relocated"] = s.relocated;
         d["loose_localizations"] = s.loose_localizations;
+        d["origins_elided"] = s.origins_elided;
+        d["origin_bytes_uploaded"] = s.origin_bytes_uploaded;
+        d["origin_pass_seconds"] = s.origin_pass_seconds;
         return d;
       })
       // First-K lost-walk capture: (k, 4) array of

@@ -92,6 +92,33 @@ class TallyEngine:
     def max_steps(self, v: int) -> None:
         self._eng.max_steps = v
 
+    # Origin elision (GPU engine): move() skips the upload of origins that
+    # are bit-identical to the previous move's destinations.  Results do
+    # not depend on any of the three; see docs/CONFIG.md.
+    @property
+    def origin_elide(self) -> bool:
+        return self._eng.origin_elide
+
+    @origin_elide.setter
+    def origin_elide(self, v: bool) -> None:
+        self._eng.origin_elide = bool(v)
+
+    @property
+    def origin_threads(self) -> int:
+        return self._eng.origin_threads
+
+    @origin_threads.setter
+    def origin_threads(self, v: int) -> None:
+        self._eng.origin_threads = int(v)
+
+    @property
+    def origin_chunk(self) -> int:
+        return self._eng.origin_chunk
+
+    @origin_chunk.setter
+    def origin_chunk(self, v: int) -> None:
+        self._eng.origin_chunk = int(v)
+
     def copy_initial_position(self, positions):
         self._eng.copy_initial_position(positions)
 

@@ -25,6 +25,7 @@ SOURCES = [
     "csrc/core/osh_io.cpp",
     "csrc/core/osh_omegah.cpp",
     "csrc/core/engine_cpu.cpp",
+    "csrc/core/origin_delta.cpp",
     "csrc/core/partition.cpp",
     "csrc/comm/comm_tcp.cpp",
     "csrc/comm/comm_rccl.hip",
@@ -39,6 +40,7 @@ HEADERS = [
     "csrc/core/mesh.h",
     "csrc/core/walk.h",
     "csrc/core/engine.h",
+    "csrc/core/origin_delta.h",
     "csrc/comm/comm.h",
     "csrc/core/partition_engine.h",
     "csrc/api/PumiTally.h",
