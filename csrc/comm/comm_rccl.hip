@@ -12,6 +12,7 @@
 // pumipic::Library / picparts migration (/root/reference/src/pumitally/
 // PumiTallyImpl.cpp:238-241,454).
 #include "comm.h"
+#include "../hip/hip_util.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -23,15 +24,6 @@
 namespace pumitally {
 
 namespace {
-
-#define PT_HIP_CK(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess)                                                      \
-      throw std::runtime_error(std::string("HIP error at comm_rccl:") +        \
-                               std::to_string(__LINE__) + ": " +               \
-                               hipGetErrorString(_e));                         \
-  } while (0)
 
 #define PT_NCCL_CK(expr)                                                       \
   do {                                                                         \
@@ -47,20 +39,17 @@ public:
   RcclComm(int rank, int world, const std::string &addr, int port, int device)
       : device_(device) {
     boot_ = make_tcp_comm(rank, world, addr, port);
-    PT_HIP_CK(hipSetDevice(device_));
+    PT_HIP_CHECK(hipSetDevice(device_));
     ncclUniqueId id;
     if (rank == 0) PT_NCCL_CK(ncclGetUniqueId(&id));
     boot_->bcast(&id, sizeof id, 0);
     PT_NCCL_CK(ncclCommInitRank(&comm_, world, id, rank));
-    PT_HIP_CK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    stream_.create();
   }
 
   ~RcclComm() override {
     (void)hipSetDevice(device_);
     if (comm_) (void)ncclCommDestroy(comm_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-    if (d_a_) (void)hipFree(d_a_);
-    if (d_b_) (void)hipFree(d_b_);
   }
 
   int rank() const override { return boot_->rank(); }
@@ -70,11 +59,11 @@ public:
   void allreduce_sum(double *data, int64_t n) override {
     // host buffer: stage through device scratch; xGMI all-reduce is far
     // faster than the TCP hub for the nelems-sized flux arrays
-    PT_HIP_CK(hipSetDevice(device_));
-    grow(&d_a_, &cap_a_, n);
-    PT_HIP_CK(hipMemcpy(d_a_, data, n * 8, hipMemcpyHostToDevice));
+    PT_HIP_CHECK(hipSetDevice(device_));
+    d_a_.reserve(n);
+    PT_HIP_CHECK(hipMemcpy(d_a_, data, n * 8, hipMemcpyHostToDevice));
     allreduce_sum_device(d_a_, n);
-    PT_HIP_CK(hipMemcpy(data, d_a_, n * 8, hipMemcpyDeviceToHost));
+    PT_HIP_CHECK(hipMemcpy(data, d_a_, n * 8, hipMemcpyDeviceToHost));
   }
 
   void allreduce_sum(int64_t *data, int64_t n) override {
@@ -96,7 +85,7 @@ public:
   std::vector<double> alltoallv(
       const double *send, const std::vector<int64_t> &send_counts) override {
     // host-buffer convenience: exchange counts over TCP, data over xGMI
-    PT_HIP_CK(hipSetDevice(device_));
+    PT_HIP_CHECK(hipSetDevice(device_));
     const int w = world();
     std::vector<int64_t> flat(w * w, 0);
     for (int r = 0; r < w; ++r) flat[(int64_t)rank() * w + r] = send_counts[r];
@@ -106,34 +95,35 @@ public:
     int64_t stot = 0, rtot = 0;
     for (int64_t c : send_counts) stot += c;
     for (int64_t c : recv_counts) rtot += c;
-    grow(&d_a_, &cap_a_, stot);
-    PT_HIP_CK(hipMemcpy(d_a_, send, stot * 8, hipMemcpyHostToDevice));
+    d_a_.reserve(stot);
+    PT_HIP_CHECK(hipMemcpy(d_a_, send, stot * 8, hipMemcpyHostToDevice));
     double *d_recv = nullptr;
     alltoallv_device(d_a_, send_counts, recv_counts, &d_recv);
     std::vector<double> out(rtot);
     if (rtot)
-      PT_HIP_CK(hipMemcpy(out.data(), d_recv, rtot * 8, hipMemcpyDeviceToHost));
+      PT_HIP_CHECK(
+          hipMemcpy(out.data(), d_recv, rtot * 8, hipMemcpyDeviceToHost));
     return out;
   }
 
   bool has_device_collectives() const override { return true; }
 
   void allreduce_sum_device(double *d_data, int64_t n) override {
-    PT_HIP_CK(hipSetDevice(device_));
+    PT_HIP_CHECK(hipSetDevice(device_));
     PT_NCCL_CK(ncclAllReduce(d_data, d_data, (size_t)n, ncclDouble, ncclSum,
                              comm_, stream_));
-    PT_HIP_CK(hipStreamSynchronize(stream_));
+    PT_HIP_CHECK(hipStreamSynchronize(stream_));
   }
 
   int64_t alltoallv_device(const double *d_send,
                            const std::vector<int64_t> &send_counts,
                            const std::vector<int64_t> &recv_counts,
                            double **d_recv) override {
-    PT_HIP_CK(hipSetDevice(device_));
+    PT_HIP_CHECK(hipSetDevice(device_));
     const int w = world();
     int64_t rtot = 0;
     for (int64_t c : recv_counts) rtot += c;
-    grow(&d_b_, &cap_b_, rtot);
+    d_b_.reserve(rtot);
     PT_NCCL_CK(ncclGroupStart());
     int64_t soff = 0, roff = 0;
     for (int r = 0; r < w; ++r) {
@@ -147,25 +137,17 @@ public:
       roff += recv_counts[r];
     }
     PT_NCCL_CK(ncclGroupEnd());
-    PT_HIP_CK(hipStreamSynchronize(stream_));
+    PT_HIP_CHECK(hipStreamSynchronize(stream_));
     *d_recv = d_b_;
     return rtot;
   }
 
 private:
-  void grow(double **p, int64_t *cap, int64_t n) {
-    if (n <= *cap) return;
-    if (*p) PT_HIP_CK(hipFree(*p));
-    *cap = n + n / 4;
-    PT_HIP_CK(hipMalloc((void **)p, *cap * 8));
-  }
-
   int device_;
   std::unique_ptr<Comm> boot_;
   ncclComm_t comm_ = nullptr;
-  hipStream_t stream_ = nullptr;
-  double *d_a_ = nullptr, *d_b_ = nullptr; // staging / recv scratch
-  int64_t cap_a_ = 0, cap_b_ = 0;
+  Stream stream_;
+  DeviceBuffer<double> d_a_, d_b_; // staging / recv scratch
 };
 
 } // namespace

@@ -33,6 +33,7 @@
 #include "../core/engine.h"
 #include "../core/origin_delta.h"
 #include "../core/walk.h"
+#include "hip_util.h"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -50,15 +51,6 @@
 #include <vector>
 
 namespace pumitally {
-
-#define PT_HIP_CHECK(expr)                                                     \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess)                                                      \
-      throw std::runtime_error(std::string("HIP error at " __FILE__ ":") +     \
-                               std::to_string(__LINE__) + ": " +               \
-                               hipGetErrorString(_e));                         \
-  } while (0)
 
 namespace {
 
@@ -548,12 +540,6 @@ int grid_blocks(int64_t work) {
   return (int)((blocks + 7) / 8 * 8);
 }
 
-template <class T> T *dmalloc(int64_t count) {
-  void *p = nullptr;
-  PT_HIP_CHECK(hipMalloc(&p, count * sizeof(T)));
-  return (T *)p;
-}
-
 class GpuEngine final : public Engine {
 public:
   GpuEngine(Mesh mesh, int64_t n, int device, int groups, int scores)
@@ -562,66 +548,41 @@ public:
     nscores = scores < 1 ? 1 : scores;
     PT_HIP_CHECK(hipSetDevice(device));
     device_ = device;
-    PT_HIP_CHECK(hipStreamCreateWithFlags(&s_copy_, hipStreamNonBlocking));
-    PT_HIP_CHECK(hipStreamCreateWithFlags(&s_comp_, hipStreamNonBlocking));
-    for (auto &ev : copy_ev_)
-      PT_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (auto &ev : kernels_done_)
-      PT_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    s_copy_.create();
+    s_comp_.create();
+    for (auto &ev : copy_ev_) ev.create();
+    for (auto &ev : kernels_done_) ev.create();
 
     // Mesh upload (once).
-    d_planes_ = dmalloc<Plane>(mesh_.nelems * 4);
-    d_planes32_ = dmalloc<Plane32>(mesh_.nelems * 4);
-    d_nbr_ = dmalloc<int32_t>(mesh_.nelems * 4);
-    d_cell_start_ = dmalloc<int32_t>(mesh_.grid.cell_start.size());
-    d_cell_tets_ = dmalloc<int32_t>(mesh_.grid.cell_tets.size() + 1);
-    PT_HIP_CHECK(hipMemcpy(d_planes_, mesh_.planes.data(),
-                           mesh_.nelems * 4 * sizeof(Plane), hipMemcpyHostToDevice));
-    PT_HIP_CHECK(hipMemcpy(d_planes32_, mesh_.planes32.data(),
-                           mesh_.nelems * 4 * sizeof(Plane32), hipMemcpyHostToDevice));
-    PT_HIP_CHECK(hipMemcpy(d_nbr_, mesh_.nbr.data(),
-                           mesh_.nelems * 4 * sizeof(int32_t), hipMemcpyHostToDevice));
-    PT_HIP_CHECK(hipMemcpy(d_cell_start_, mesh_.grid.cell_start.data(),
-                           mesh_.grid.cell_start.size() * sizeof(int32_t),
-                           hipMemcpyHostToDevice));
+    d_planes_ = upload(mesh_.planes);
+    d_planes32_ = upload(mesh_.planes32);
+    d_nbr_ = upload(mesh_.nbr);
+    d_cell_start_ = upload(mesh_.grid.cell_start);
+    d_cell_tets_.allocate(mesh_.grid.cell_tets.size() + 1);
     PT_HIP_CHECK(hipMemcpy(d_cell_tets_, mesh_.grid.cell_tets.data(),
                            mesh_.grid.cell_tets.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice));
-    if (!mesh_.face_bc_bits.empty()) {
-      d_face_bc_ = dmalloc<uint32_t>(mesh_.face_bc_bits.size());
-      PT_HIP_CHECK(hipMemcpy(d_face_bc_, mesh_.face_bc_bits.data(),
-                             mesh_.face_bc_bits.size() * sizeof(uint32_t),
-                             hipMemcpyHostToDevice));
-    }
+    d_face_bc_ = upload(mesh_.face_bc_bits); // empty: stays null
     if (mesh_.has_periodic()) {
-      d_pidx_ = dmalloc<int32_t>(mesh_.periodic_idx.size());
-      d_pelem_ = dmalloc<int32_t>(mesh_.periodic_elem.size());
-      d_pshift_ = dmalloc<double>(mesh_.periodic_shift.size());
-      PT_HIP_CHECK(hipMemcpy(d_pidx_, mesh_.periodic_idx.data(),
-                             mesh_.periodic_idx.size() * 4,
-                             hipMemcpyHostToDevice));
-      PT_HIP_CHECK(hipMemcpy(d_pelem_, mesh_.periodic_elem.data(),
-                             mesh_.periodic_elem.size() * 4,
-                             hipMemcpyHostToDevice));
-      PT_HIP_CHECK(hipMemcpy(d_pshift_, mesh_.periodic_shift.data(),
-                             mesh_.periodic_shift.size() * 8,
-                             hipMemcpyHostToDevice));
+      d_pidx_ = upload(mesh_.periodic_idx);
+      d_pelem_ = upload(mesh_.periodic_elem);
+      d_pshift_ = upload(mesh_.periodic_shift);
     }
     grid_view_ = GridView{mesh_.grid.nx, mesh_.grid.ny, mesh_.grid.nz,
                           mesh_.grid.lo,  mesh_.grid.inv_h,
                           d_cell_start_,  d_cell_tets_};
 
     // Particle state (slot order) + slot->caller map.
-    d_pos_ = dmalloc<double>(n_ * 3);
-    d_elem_ = dmalloc<int32_t>(n_);
-    d_escaped_ = dmalloc<uint8_t>(n_);
-    d_s2c_ = dmalloc<int32_t>(n_);
+    d_pos_.allocate(n_ * 3);
+    d_elem_.allocate(n_);
+    d_escaped_.allocate(n_);
+    d_s2c_.allocate(n_);
     fsz_ = mesh_.nelems * ngroups * nscores;
     slices_ = flux_slices(fsz_);
-    d_flux_ = dmalloc<double>(fsz_ * slices_);
-    d_lost_ = dmalloc<unsigned long long>(1);
-    d_loose_ = dmalloc<unsigned long long>(1);
-    d_lostrec_ = dmalloc<double>((int64_t)kMaxLostRecords * 4);
+    d_flux_.allocate(fsz_ * slices_);
+    d_lost_.allocate(1);
+    d_loose_.allocate(1);
+    d_lostrec_.allocate((int64_t)kMaxLostRecords * 4);
     PT_HIP_CHECK(hipMemset(d_flux_, 0, fsz_ * slices_ * sizeof(double)));
     PT_HIP_CHECK(hipMemset(d_lost_, 0, sizeof(unsigned long long)));
     PT_HIP_CHECK(hipMemset(d_loose_, 0, sizeof(unsigned long long)));
@@ -630,11 +591,11 @@ public:
 
     // Parity double-buffered input staging.
     for (int p = 0; p < 2; ++p) {
-      d_origin_[p] = dmalloc<double>(n_ * 3);
-      d_dest_[p] = dmalloc<double>(n_ * 3);
-      d_flying_[p] = dmalloc<int8_t>(n_);
-      d_weights_[p] = dmalloc<double>(n_);
-      d_groups_[p] = ngroups > 1 ? dmalloc<uint16_t>(n_) : nullptr;
+      d_origin_[p].allocate(n_ * 3);
+      d_dest_[p].allocate(n_ * 3);
+      d_flying_[p].allocate(n_);
+      d_weights_[p].allocate(n_);
+      if (ngroups > 1) d_groups_[p].allocate(n_);
       // d_resp_ is lazy-allocated on the first move() that passes
       // responses (valid even with nscores==1: a single per-particle
       // response multiplier).
@@ -643,20 +604,20 @@ public:
     // Spatial-sort scratch.
     sort_every_ = sort_every();
     if (sort_every_ > 0) {
-      d_keys_ = dmalloc<uint64_t>(n_);
-      d_keys2_ = dmalloc<uint64_t>(n_);
-      d_vals_ = dmalloc<int32_t>(n_);
-      d_order_ = dmalloc<int32_t>(n_);
-      d_pos2_ = dmalloc<double>(n_ * 3);
-      d_elem2_ = dmalloc<int32_t>(n_);
-      d_esc2_ = dmalloc<uint8_t>(n_);
-      d_s2c2_ = dmalloc<int32_t>(n_);
+      d_keys_.allocate(n_);
+      d_keys2_.allocate(n_);
+      d_vals_.allocate(n_);
+      d_order_.allocate(n_);
+      d_pos2_.allocate(n_ * 3);
+      d_elem2_.allocate(n_);
+      d_esc2_.allocate(n_);
+      d_s2c2_.allocate(n_);
       size_t bytes = 0;
       PT_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-          nullptr, bytes, d_keys_, d_keys2_, d_vals_, d_order_, (int)n_, 0, 64,
-          s_comp_));
+          nullptr, bytes, d_keys_.get(), d_keys2_.get(), d_vals_.get(),
+          d_order_.get(), (int)n_, 0, 64, s_comp_));
       sorttmp_bytes_ = bytes;
-      PT_HIP_CHECK(hipMalloc(&d_sorttmp_, bytes ? bytes : 1));
+      d_sorttmp_.allocate(bytes ? bytes : 1);
       const Vec3 ext = mesh_.bbox_hi - mesh_.bbox_lo;
       sort_scale_ = Vec3{ext.x > 0 ? 2097151.0 / ext.x : 0.0,
                          ext.y > 0 ? 2097151.0 / ext.y : 0.0,
@@ -679,29 +640,7 @@ public:
   ~GpuEngine() override {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    for (void *p : {(void *)d_planes_, (void *)d_planes32_, (void *)d_nbr_,
-                    (void *)d_cell_start_, (void *)d_cell_tets_,
-                    (void *)d_pos_, (void *)d_elem_, (void *)d_escaped_,
-                    (void *)d_s2c_, (void *)d_flux_, (void *)d_lost_,
-                    (void *)d_loose_, (void *)d_lostrec_,
-                    (void *)d_origin_[0], (void *)d_origin_[1],
-                    (void *)d_dest_[0], (void *)d_dest_[1],
-                    (void *)d_flying_[0], (void *)d_flying_[1],
-                    (void *)d_weights_[0], (void *)d_weights_[1],
-                    (void *)d_groups_[0], (void *)d_groups_[1],
-                    (void *)d_resp_[0], (void *)d_resp_[1],
-                    (void *)d_bsum_, (void *)d_bsq_, (void *)d_face_bc_,
-                    (void *)d_pidx_, (void *)d_pelem_, (void *)d_pshift_,
-                    (void *)d_keys_, (void *)d_keys2_, (void *)d_vals_,
-                    (void *)d_order_, (void *)d_pos2_, (void *)d_elem2_,
-                    (void *)d_esc2_, (void *)d_s2c2_, d_sorttmp_})
-      if (p) (void)hipFree(p);
-    free_wr();
-    free_patch();
-    for (auto &ev : copy_ev_) (void)hipEventDestroy(ev);
-    for (auto &ev : kernels_done_) (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(s_copy_);
-    (void)hipStreamDestroy(s_comp_);
+    // members release themselves: buffers first, then events and streams
   }
 
   int64_t num_particles() const override { return n_; }
@@ -738,7 +677,7 @@ public:
     // WAR fence: buffer set p was last read by the kernels of the move
     // two calls ago; its copies must wait for them.
     PT_HIP_CHECK(hipStreamWaitEvent(s_copy_, kernels_done_[p], 0));
-    if (responses && !d_resp_[p]) d_resp_[p] = dmalloc<double>(n_ * nscores);
+    if (responses && !d_resp_[p]) d_resp_[p].allocate(n_ * nscores);
     // Origin elision applies when the host shadow holds exactly what the
     // previous call staged into d_dest_[p^1]; every other case (continue
     // semantics, switch off, back-off, first move) takes the plain upload.
@@ -750,13 +689,7 @@ public:
         stage(origin, n * 3 * sizeof(double), d_origin_[p], s_copy_);
         stats_.origin_bytes_uploaded += n * 3 * (int64_t)sizeof(double);
       }
-      stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
-      stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
-      stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
-      if (groups && d_groups_[p])
-        stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
-      if (responses)
-        stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+      stage_inputs(p, dest, flying, weights, groups, responses, n);
       // d_dest_[p] no longer matches the shadow (move_continue marks it
       // invalid rather than paying for an update it may never use) ...
       shadow_valid_ = false;
@@ -804,44 +737,32 @@ public:
   // Persistent scratch for walk_raw.  The partitioned driver calls
   // walk_raw once per exchange round; per-call hipMalloc/hipFree pairs
   // would device-sync every round, so the buffers are grown once and
-  // reused (freed in the dtor).
+  // reused (released with the engine).
   struct WalkRawScratch {
     int64_t cap = 0;
-    double *pos = nullptr, *dest = nullptr, *w = nullptr, *out_pos = nullptr,
-           *resp = nullptr, *out_dest = nullptr;
-    int32_t *elem = nullptr, *out_elem = nullptr;
-    int8_t *status = nullptr;
-    uint16_t *groups = nullptr;
-    double *in_t = nullptr, *out_o = nullptr, *out_t = nullptr;
-    int32_t *in_prev = nullptr, *out_prev = nullptr;
+    DeviceBuffer<double> pos, dest, w, out_pos, resp, out_dest;
+    DeviceBuffer<int32_t> elem, out_elem;
+    DeviceBuffer<int8_t> status;
+    DeviceBuffer<uint16_t> groups;
+    DeviceBuffer<double> in_t, out_o, out_t;
+    DeviceBuffer<int32_t> in_prev, out_prev;
   };
 
   void ensure_wr_cap(int64_t n, bool need_groups, bool need_resp) {
     if (n > wr_.cap) {
-      free_wr();
-      wr_.cap = n + n / 4; // headroom against round-to-round growth
-      wr_.pos = dmalloc<double>(wr_.cap * 3);
-      wr_.dest = dmalloc<double>(wr_.cap * 3);
-      wr_.w = dmalloc<double>(wr_.cap);
-      wr_.out_pos = dmalloc<double>(wr_.cap * 3);
-      wr_.elem = dmalloc<int32_t>(wr_.cap);
-      wr_.out_elem = dmalloc<int32_t>(wr_.cap);
-      wr_.status = dmalloc<int8_t>(wr_.cap);
+      wr_ = WalkRawScratch{}; // drops the optional buffers too
+      const int64_t cap = n + n / 4; // headroom against round-to-round growth
+      wr_.pos.allocate(cap * 3);
+      wr_.dest.allocate(cap * 3);
+      wr_.w.allocate(cap);
+      wr_.out_pos.allocate(cap * 3);
+      wr_.elem.allocate(cap);
+      wr_.out_elem.allocate(cap);
+      wr_.status.allocate(cap);
+      wr_.cap = cap;
     }
-    if (need_groups && !wr_.groups) wr_.groups = dmalloc<uint16_t>(wr_.cap);
-    if (need_resp && !wr_.resp) wr_.resp = dmalloc<double>(wr_.cap * nscores);
-  }
-
-  void free_wr() {
-    for (void *q : {(void *)wr_.pos, (void *)wr_.dest, (void *)wr_.w,
-                    (void *)wr_.out_pos, (void *)wr_.elem,
-                    (void *)wr_.out_elem, (void *)wr_.status,
-                    (void *)wr_.groups, (void *)wr_.resp,
-                    (void *)wr_.out_dest, (void *)wr_.in_t,
-                    (void *)wr_.out_o, (void *)wr_.out_t,
-                    (void *)wr_.in_prev, (void *)wr_.out_prev})
-      if (q) (void)hipFree(q);
-    wr_ = WalkRawScratch{};
+    if (need_groups && !wr_.groups) wr_.groups.allocate(wr_.cap);
+    if (need_resp && !wr_.resp) wr_.resp.allocate(wr_.cap * nscores);
   }
 
   void walk_raw(int64_t n, const double *pos, const double *dest,
@@ -855,15 +776,14 @@ public:
                 int32_t *out_prev = nullptr) override {
     if (n == 0) return;
     PT_HIP_CHECK(hipSetDevice(device_));
-    const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
     ensure_wr_cap(n, groups != nullptr, responses != nullptr);
     const bool resume = in_t || in_prev || out_o || out_t || out_prev;
     if (resume && !wr_.in_t) {
-      wr_.in_t = dmalloc<double>(wr_.cap);
-      wr_.in_prev = dmalloc<int32_t>(wr_.cap);
-      wr_.out_o = dmalloc<double>(wr_.cap * 3);
-      wr_.out_t = dmalloc<double>(wr_.cap);
-      wr_.out_prev = dmalloc<int32_t>(wr_.cap);
+      wr_.in_t.allocate(wr_.cap);
+      wr_.in_prev.allocate(wr_.cap);
+      wr_.out_o.allocate(wr_.cap * 3);
+      wr_.out_t.allocate(wr_.cap);
+      wr_.out_prev.allocate(wr_.cap);
     }
     if (in_t)
       PT_HIP_CHECK(hipMemcpy(wr_.in_t, in_t, n * 8, hipMemcpyHostToDevice));
@@ -883,28 +803,14 @@ public:
     if (responses)
       PT_HIP_CHECK(hipMemcpy(wr_.resp, responses, n * nscores * 8,
                              hipMemcpyHostToDevice));
-    if (out_dest && !wr_.out_dest) wr_.out_dest = dmalloc<double>(wr_.cap * 3);
-    if (walk_fp32)
-      k_walk_raw<true><<<grid_blocks(n), kBlock, 0, s_comp_>>>(
-          d_planes_, d_planes32_, d_nbr_, wr_.pos, wr_.dest, wr_.elem, wr_.w,
-          dg, dr, wr_.out_pos, wr_.out_elem, wr_.status,
-          out_dest ? wr_.out_dest : nullptr, d_flux_, d_lost_,
-          d_lostrec_, n,
-          steps, reflective, d_face_bc_, ngroups, mesh_.nelems, nscores,
-          d_pidx_, d_pelem_, d_pshift_, in_t ? wr_.in_t : nullptr,
-          in_prev ? wr_.in_prev : nullptr, out_o ? wr_.out_o : nullptr,
-          out_t ? wr_.out_t : nullptr, out_prev ? wr_.out_prev : nullptr);
-    else
-      k_walk_raw<false><<<grid_blocks(n), kBlock, 0, s_comp_>>>(
-          d_planes_, d_planes32_, d_nbr_, wr_.pos, wr_.dest, wr_.elem, wr_.w,
-          dg, dr, wr_.out_pos, wr_.out_elem, wr_.status,
-          out_dest ? wr_.out_dest : nullptr, d_flux_, d_lost_,
-          d_lostrec_, n,
-          steps, reflective, d_face_bc_, ngroups, mesh_.nelems, nscores,
-          d_pidx_, d_pelem_, d_pshift_, in_t ? wr_.in_t : nullptr,
-          in_prev ? wr_.in_prev : nullptr, out_o ? wr_.out_o : nullptr,
-          out_t ? wr_.out_t : nullptr, out_prev ? wr_.out_prev : nullptr);
-    PT_HIP_CHECK(hipGetLastError());
+    if (out_dest && !wr_.out_dest) wr_.out_dest.allocate(wr_.cap * 3);
+    launch_walk_raw(n, wr_.pos, wr_.dest, wr_.elem, wr_.w, wr_.out_pos,
+                    wr_.out_elem, wr_.status, dg, dr,
+                    out_dest ? wr_.out_dest : nullptr,
+                    in_t ? wr_.in_t : nullptr,
+                    in_prev ? wr_.in_prev : nullptr,
+                    out_o ? wr_.out_o : nullptr, out_t ? wr_.out_t : nullptr,
+                    out_prev ? wr_.out_prev : nullptr);
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
     PT_HIP_CHECK(hipMemcpy(out_pos, wr_.out_pos, n * 3 * 8,
                            hipMemcpyDeviceToHost));
@@ -938,22 +844,9 @@ public:
                        int32_t *d_out_prev = nullptr) override {
     if (n == 0) return;
     PT_HIP_CHECK(hipSetDevice(device_));
-    const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
-    if (walk_fp32)
-      k_walk_raw<true><<<grid_blocks(n), kBlock, 0, s_comp_>>>(
-          d_planes_, d_planes32_, d_nbr_, d_pos, d_dest, d_elem, d_weights,
-          d_groups, d_responses, d_out_pos, d_out_elem, d_out_status,
-          d_out_dest, d_flux_, d_lost_, d_lostrec_, n, steps, reflective,
-          d_face_bc_, ngroups, mesh_.nelems, nscores, d_pidx_, d_pelem_,
-          d_pshift_, d_in_t, d_in_prev, d_out_o, d_out_t, d_out_prev);
-    else
-      k_walk_raw<false><<<grid_blocks(n), kBlock, 0, s_comp_>>>(
-          d_planes_, d_planes32_, d_nbr_, d_pos, d_dest, d_elem, d_weights,
-          d_groups, d_responses, d_out_pos, d_out_elem, d_out_status,
-          d_out_dest, d_flux_, d_lost_, d_lostrec_, n, steps, reflective,
-          d_face_bc_, ngroups, mesh_.nelems, nscores, d_pidx_, d_pelem_,
-          d_pshift_, d_in_t, d_in_prev, d_out_o, d_out_t, d_out_prev);
-    PT_HIP_CHECK(hipGetLastError());
+    launch_walk_raw(n, d_pos, d_dest, d_elem, d_weights, d_out_pos, d_out_elem,
+                    d_out_status, d_groups, d_responses, d_out_dest, d_in_t,
+                    d_in_prev, d_out_o, d_out_t, d_out_prev);
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
   }
 
@@ -962,8 +855,8 @@ public:
     sync();
     const int64_t fsz = fsz_;
     if (!d_bsum_) {
-      d_bsum_ = dmalloc<double>(fsz);
-      d_bsq_ = dmalloc<double>(fsz);
+      d_bsum_.allocate(fsz);
+      d_bsq_.allocate(fsz);
       PT_HIP_CHECK(hipMemset(d_bsum_, 0, fsz * sizeof(double)));
       PT_HIP_CHECK(hipMemset(d_bsq_, 0, fsz * sizeof(double)));
     }
@@ -1103,6 +996,19 @@ private:
     PT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
   }
 
+  // Everything a move stages besides the origins, into buffer set p.
+  void stage_inputs(int p, const double *dest, const int8_t *flying,
+                    const double *weights, const uint16_t *groups,
+                    const double *responses, int64_t n) {
+    stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
+    stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
+    stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
+    if (groups && d_groups_[p])
+      stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
+    if (responses)
+      stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+  }
+
   // ---- origin elision ---------------------------------------------------
   //
   // The headline move() is bound by the host-to-device link, and 240 of its
@@ -1179,29 +1085,18 @@ private:
     if (!shadow_) shadow_.reset(new double[n * 3]);
   }
 
-  void free_patch() {
-    if (h_patch_idx_) (void)hipHostFree(h_patch_idx_);
-    if (h_patch_xyz_) (void)hipHostFree(h_patch_xyz_);
-    if (d_patch_idx_) (void)hipFree(d_patch_idx_);
-    if (d_patch_xyz_) (void)hipFree(d_patch_xyz_);
-    h_patch_idx_ = d_patch_idx_ = nullptr;
-    h_patch_xyz_ = d_patch_xyz_ = nullptr;
-    patch_cap_ = 0;
-  }
-
   void ensure_patch(int64_t need) {
     if (need <= patch_cap_) return;
     PT_HIP_CHECK(hipStreamSynchronize(s_copy_)); // scatters may still read
-    free_patch();
-    void *hi = nullptr, *hx = nullptr;
-    PT_HIP_CHECK(hipHostMalloc(&hi, need * sizeof(int32_t),
-                               hipHostMallocDefault));
-    h_patch_idx_ = (int32_t *)hi;
-    PT_HIP_CHECK(hipHostMalloc(&hx, need * 3 * sizeof(double),
-                               hipHostMallocDefault));
-    h_patch_xyz_ = (double *)hx;
-    d_patch_idx_ = dmalloc<int32_t>(need);
-    d_patch_xyz_ = dmalloc<double>(need * 3);
+    patch_cap_ = 0;
+    h_patch_idx_.reset();
+    h_patch_xyz_.reset();
+    d_patch_idx_.reset();
+    d_patch_xyz_.reset();
+    h_patch_idx_.allocate(need);
+    h_patch_xyz_.allocate(need * 3);
+    d_patch_idx_.allocate(need);
+    d_patch_xyz_.allocate(need * 3);
     patch_cap_ = need;
   }
 
@@ -1226,13 +1121,7 @@ private:
     // (Measured on MI355X: interleaving per-chunk slices of these copies
     // with the pass averaged 8.05 ms/step over a thread x chunk sweep,
     // this order 7.05; profiles/README.md.)
-    stage(dest, n * 3 * sizeof(double), d_dest_[p], s_copy_);
-    stage(flying, n * sizeof(int8_t), d_flying_[p], s_copy_);
-    stage(weights, n * sizeof(double), d_weights_[p], s_copy_);
-    if (groups && d_groups_[p])
-      stage(groups, n * sizeof(uint16_t), d_groups_[p], s_copy_);
-    if (responses)
-      stage(responses, n * nscores * sizeof(double), d_resp_[p], s_copy_);
+    stage_inputs(p, dest, flying, weights, groups, responses, n);
     int64_t region = 0, uploaded = 0;
     for (int64_t lo = 0; lo < n; lo += chunk) {
       const int64_t hi = std::min(n, lo + chunk);
@@ -1281,6 +1170,25 @@ private:
     } else {
       elide_backoff_ = kElideBackoffFirst;
     }
+  }
+
+  // The k_walk_raw launch of walk_raw and walk_raw_device (device pointers,
+  // argument order of walk_raw_device).
+  void launch_walk_raw(int64_t n, const double *pos, const double *dest,
+                       const int32_t *elem, const double *weights,
+                       double *out_pos, int32_t *out_elem, int8_t *out_status,
+                       const uint16_t *groups, const double *resp,
+                       double *out_dest, const double *in_t,
+                       const int32_t *in_prev, double *out_o, double *out_t,
+                       int32_t *out_prev) {
+    const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
+    const auto kernel = walk_fp32 ? k_walk_raw<true> : k_walk_raw<false>;
+    kernel<<<grid_blocks(n), kBlock, 0, s_comp_>>>(
+        d_planes_, d_planes32_, d_nbr_, pos, dest, elem, weights, groups, resp,
+        out_pos, out_elem, out_status, out_dest, d_flux_, d_lost_, d_lostrec_,
+        n, steps, reflective, d_face_bc_, ngroups, mesh_.nelems, nscores,
+        d_pidx_, d_pelem_, d_pshift_, in_t, in_prev, out_o, out_t, out_prev);
+    PT_HIP_CHECK(hipGetLastError());
   }
 
   template <bool F32, bool Scored, bool Periodic, bool Agg = false>
@@ -1341,8 +1249,8 @@ private:
     PT_HIP_CHECK(hipGetLastError());
     size_t bytes = sorttmp_bytes_;
     PT_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-        d_sorttmp_, bytes, d_keys_, d_keys2_, d_vals_, d_order_, (int)n_, 0,
-        64, s_comp_));
+        d_sorttmp_, bytes, d_keys_.get(), d_keys2_.get(), d_vals_.get(),
+        d_order_.get(), (int)n_, 0, 64, s_comp_));
     k_permute_state<<<grid_blocks(n_), kBlock, 0, s_comp_>>>(
         d_order_, d_pos_, d_elem_, d_escaped_, d_s2c_, d_pos2_, d_elem2_,
         d_esc2_, d_s2c2_, n_);
@@ -1392,51 +1300,50 @@ private:
   std::unique_ptr<double[]> shadow_;
   bool shadow_valid_ = false;
   std::unique_ptr<OriginDeltaPool> delta_pool_;
-  int32_t *h_patch_idx_ = nullptr, *d_patch_idx_ = nullptr;
-  double *h_patch_xyz_ = nullptr, *d_patch_xyz_ = nullptr;
   int64_t patch_cap_ = 0;
   int elide_skip_ = 0;                     // plain moves left in a back-off
   int elide_backoff_ = kElideBackoffFirst; // length of the next back-off
 
-  hipStream_t s_copy_{}, s_comp_{};
-  std::array<hipEvent_t, 2> copy_ev_{};
-  std::array<hipEvent_t, 2> kernels_done_{};
+  // Streams and events come before every buffer, so they are destroyed
+  // after all of them.
+  Stream s_copy_, s_comp_;
+  std::array<Event, 2> copy_ev_;
+  std::array<Event, 2> kernels_done_;
 
-  Plane *d_planes_ = nullptr;
-  Plane32 *d_planes32_ = nullptr;
-  int32_t *d_nbr_ = nullptr;
-  int32_t *d_cell_start_ = nullptr;
-  int32_t *d_cell_tets_ = nullptr;
+  PinnedBuffer<int32_t> h_patch_idx_;
+  PinnedBuffer<double> h_patch_xyz_;
+  DeviceBuffer<int32_t> d_patch_idx_;
+  DeviceBuffer<double> d_patch_xyz_;
+
+  DeviceBuffer<Plane> d_planes_;
+  DeviceBuffer<Plane32> d_planes32_;
+  DeviceBuffer<int32_t> d_nbr_, d_cell_start_, d_cell_tets_;
   GridView grid_view_{};
 
-  double *d_pos_ = nullptr;
-  int32_t *d_elem_ = nullptr;
-  uint8_t *d_escaped_ = nullptr;
-  int32_t *d_s2c_ = nullptr;
-  double *d_flux_ = nullptr;
-  unsigned long long *d_lost_ = nullptr;
-  unsigned long long *d_loose_ = nullptr;
-  double *d_lostrec_ = nullptr;
-  double *d_origin_[2] = {nullptr, nullptr};
-  uint16_t *d_groups_[2] = {nullptr, nullptr};
-  double *d_resp_[2] = {nullptr, nullptr};
-  double *d_bsum_ = nullptr, *d_bsq_ = nullptr;
-  uint32_t *d_face_bc_ = nullptr;
-  int32_t *d_pidx_ = nullptr, *d_pelem_ = nullptr;
-  double *d_pshift_ = nullptr;
+  DeviceBuffer<double> d_pos_;
+  DeviceBuffer<int32_t> d_elem_;
+  DeviceBuffer<uint8_t> d_escaped_;
+  DeviceBuffer<int32_t> d_s2c_;
+  DeviceBuffer<double> d_flux_;
+  DeviceBuffer<unsigned long long> d_lost_, d_loose_;
+  DeviceBuffer<double> d_lostrec_;
+  DeviceBuffer<double> d_origin_[2], d_dest_[2], d_weights_[2], d_resp_[2];
+  DeviceBuffer<int8_t> d_flying_[2];
+  DeviceBuffer<uint16_t> d_groups_[2];
+  DeviceBuffer<double> d_bsum_, d_bsq_;
+  DeviceBuffer<uint32_t> d_face_bc_;
+  DeviceBuffer<int32_t> d_pidx_, d_pelem_;
+  DeviceBuffer<double> d_pshift_;
   WalkRawScratch wr_;
   int64_t nbatches_ = 0;
-  double *d_dest_[2] = {nullptr, nullptr};
-  int8_t *d_flying_[2] = {nullptr, nullptr};
-  double *d_weights_[2] = {nullptr, nullptr};
 
-  uint64_t *d_keys_ = nullptr, *d_keys2_ = nullptr;
-  int32_t *d_vals_ = nullptr, *d_order_ = nullptr;
-  double *d_pos2_ = nullptr;
-  int32_t *d_elem2_ = nullptr;
-  uint8_t *d_esc2_ = nullptr;
-  int32_t *d_s2c2_ = nullptr;
-  void *d_sorttmp_ = nullptr;
+  DeviceBuffer<uint64_t> d_keys_, d_keys2_;
+  DeviceBuffer<int32_t> d_vals_, d_order_;
+  DeviceBuffer<double> d_pos2_;
+  DeviceBuffer<int32_t> d_elem2_;
+  DeviceBuffer<uint8_t> d_esc2_;
+  DeviceBuffer<int32_t> d_s2c2_;
+  DeviceBuffer<unsigned char> d_sorttmp_;
   size_t sorttmp_bytes_ = 0;
 
   mutable EngineStats stats_;

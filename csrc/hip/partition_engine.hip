@@ -18,6 +18,7 @@
 #include "../comm/comm.h"
 #include "../core/engine.h"
 #include "../core/partition_engine.h"
+#include "hip_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,15 +32,6 @@
 namespace pumitally {
 
 namespace {
-
-#define PT_HIP_CHECK(expr)                                                     \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess)                                                      \
-      throw std::runtime_error(std::string("HIP error at partition_engine:") + \
-                               std::to_string(__LINE__) + ": " +               \
-                               hipGetErrorString(_e));                         \
-  } while (0)
 
 // Record layout (runtime width rec_w = 9 + carry_grp + nscores):
 //   [0]=gid [1..3]=pos [4]=target_gid [5..7]=dest [8]=weight
@@ -537,12 +529,6 @@ __global__ void k_part_prepare_local(
   }
 }
 
-template <class T> T *pdmalloc(int64_t count) {
-  void *p = nullptr;
-  PT_HIP_CHECK(hipMalloc(&p, count * sizeof(T)));
-  return (T *)p;
-}
-
 // ---------------------------------------------------------------------------
 // shared host-side decomposition setup
 // ---------------------------------------------------------------------------
@@ -604,101 +590,70 @@ public:
     if (!eng_->device_mesh(&dmesh_))
       throw std::runtime_error("GPU engine did not expose its device mesh");
     cs_ = (hipStream_t)dmesh_.stream; // the engine's compute stream
-    PT_HIP_CHECK(hipStreamCreateWithFlags(&s_copy_, hipStreamNonBlocking));
-    for (auto &ev : ev_in_)
-      PT_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    s_copy_.create();
+    for (auto &ev : ev_in_) ev.create();
     loc_tol_ = loc_tol_rel() * norm(full.bbox_hi - full.bbox_lo);
 
     // lookup tables
-    const int64_t nl = dec_.sub.local.nelems;
-    d_lowner_ = pdmalloc<int32_t>(nl);
-    d_l2g_ = pdmalloc<int32_t>(nl);
-    PT_HIP_CHECK(hipMemcpy(d_lowner_, dec_.lowner.data(), nl * 4,
-                           hipMemcpyHostToDevice));
-    PT_HIP_CHECK(
-        hipMemcpy(d_l2g_, dec_.l2g32.data(), nl * 4, hipMemcpyHostToDevice));
-    d_g2l_ = pdmalloc<int32_t>(nelems_global_);
-    PT_HIP_CHECK(hipMemcpy(d_g2l_, dec_.g2l.data(), nelems_global_ * 4,
-                           hipMemcpyHostToDevice));
+    d_lowner_ = upload(dec_.lowner);
+    d_l2g_ = upload(dec_.l2g32);
+    d_g2l_ = upload(dec_.g2l);
     if (!dec_.sub.foreign_gid.empty()) {
-      const int64_t nf = (int64_t)dec_.sub.foreign_gid.size();
-      std::vector<int32_t> fg(nf);
-      for (int64_t k = 0; k < nf; ++k) fg[k] = (int32_t)dec_.sub.foreign_gid[k];
-      d_fgid_ = pdmalloc<int32_t>(nf);
-      d_fowner_ = pdmalloc<int32_t>(nf);
-      PT_HIP_CHECK(hipMemcpy(d_fgid_, fg.data(), nf * 4,
-                             hipMemcpyHostToDevice));
-      PT_HIP_CHECK(hipMemcpy(d_fowner_, dec_.sub.foreign_owner.data(), nf * 4,
-                             hipMemcpyHostToDevice));
+      d_fgid_ = upload(std::vector<int32_t>(dec_.sub.foreign_gid.begin(),
+                                            dec_.sub.foreign_gid.end()));
+      d_fowner_ = upload(dec_.sub.foreign_owner);
     }
 
     // per-global-particle state
-    d_pos_ = pdmalloc<double>(n_ * 3);
-    d_elem_ = pdmalloc<int32_t>(n_);
-    d_res_ = pdmalloc<uint8_t>(n_);
-    d_esc_ = pdmalloc<uint8_t>(n_);
+    d_pos_.allocate(n_ * 3);
+    d_elem_.allocate(n_);
+    d_res_.allocate(n_);
+    d_esc_.allocate(n_);
     PT_HIP_CHECK(hipMemset(d_res_, 0, n_));
     PT_HIP_CHECK(hipMemset(d_esc_, 0, n_));
 
     // step inputs (global)
-    d_dest_ = pdmalloc<double>(n_ * 3);
-    d_fly_ = pdmalloc<int8_t>(n_);
-    d_w_ = pdmalloc<double>(n_);
+    d_dest_.allocate(n_ * 3);
+    d_fly_.allocate(n_);
+    d_w_.allocate(n_);
 
     // record widths (see the layout comment at the top)
     carry_grp_ = ngroups_ > 1;
     rec_w_ = 11 + (carry_grp_ ? 1 : 0) + nscores_;
 
     // work buffers
-    d_list_ = pdmalloc<int32_t>(n_);
-    d_dep_ = pdmalloc<double>(n_ * (rec_w_ + 1));
-    d_dest_ovr_ = pdmalloc<double>(n_ * 3);
-    d_eject_ = pdmalloc<int32_t>(n_);
+    d_list_.allocate(n_);
+    d_dep_.allocate(n_ * (rec_w_ + 1));
+    d_dest_ovr_.allocate(n_ * 3);
+    d_eject_.allocate(n_);
     // counters: [0..4] round/step counters, [8 .. 8+2*world) bucket
     // counts+cursors, then kMaxChunks per-chunk walk counters
     ctr_chunk0_ = 8 + 2 * world_;
-    d_ctr_ = pdmalloc<unsigned long long>(ctr_chunk0_ + kMaxChunks);
-    d_wpos_ = pdmalloc<double>(n_ * 3);
-    d_wdest_ = pdmalloc<double>(n_ * 3);
-    d_welem_ = pdmalloc<int32_t>(n_);
-    d_ww_ = pdmalloc<double>(n_);
-    d_wout_pos_ = pdmalloc<double>(n_ * 3);
-    d_wout_dest_ = pdmalloc<double>(n_ * 3);
-    d_wout_elem_ = pdmalloc<int32_t>(n_);
-    d_wstatus_ = pdmalloc<int8_t>(n_);
-    d_offs_ = pdmalloc<int64_t>(world_);
+    d_ctr_.allocate(ctr_chunk0_ + kMaxChunks);
+    d_wpos_.allocate(n_ * 3);
+    d_wdest_.allocate(n_ * 3);
+    d_welem_.allocate(n_);
+    d_ww_.allocate(n_);
+    d_wout_pos_.allocate(n_ * 3);
+    d_wout_dest_.allocate(n_ * 3);
+    d_wout_elem_.allocate(n_);
+    d_wstatus_.allocate(n_);
+    d_offs_.allocate(world_);
     // bitwise handoff-resume state (record layout comment above)
-    d_t0_ = pdmalloc<double>(n_);
-    d_prev_ = pdmalloc<int32_t>(n_);
-    d_wt0_ = pdmalloc<double>(n_);
-    d_wprev_ = pdmalloc<int32_t>(n_);
-    d_wout_o_ = pdmalloc<double>(n_ * 3);
-    d_wout_t_ = pdmalloc<double>(n_);
-    d_wout_prev_ = pdmalloc<int32_t>(n_);
+    d_t0_.allocate(n_);
+    d_prev_.allocate(n_);
+    d_wt0_.allocate(n_);
+    d_wprev_.allocate(n_);
+    d_wout_o_.allocate(n_ * 3);
+    d_wout_t_.allocate(n_);
+    d_wout_prev_.allocate(n_);
   }
 
   ~GpuPartitionedEngine() override {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    for (auto &ev : ev_in_) (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(s_copy_);
-    for (void *p :
-         {(void *)d_lowner_, (void *)d_l2g_, (void *)d_g2l_, (void *)d_fgid_,
-          (void *)d_fowner_, (void *)d_pos_, (void *)d_elem_, (void *)d_res_,
-          (void *)d_esc_, (void *)d_dest_, (void *)d_fly_, (void *)d_w_,
-          (void *)d_grp_, (void *)d_orig_, (void *)d_list_, (void *)d_dep_, (void *)d_dest_ovr_,
-          (void *)d_eject_, (void *)d_ctr_, (void *)d_wpos_, (void *)d_wdest_,
-          (void *)d_welem_, (void *)d_ww_, (void *)d_wgrp_,
-          (void *)d_wout_pos_, (void *)d_wout_dest_,
-          (void *)d_wout_elem_, (void *)d_wstatus_,
-          (void *)d_offs_, (void *)d_send_, (void *)d_recv_,
-          (void *)d_resp_, (void *)d_wresp_, (void *)d_frame_,
-          (void *)d_ldest_, (void *)d_lw_, (void *)d_lorig_,
-          (void *)d_lresp_, (void *)d_lfly_, (void *)d_lgrp_,
-          (void *)d_t0_, (void *)d_prev_, (void *)d_wt0_,
-          (void *)d_wprev_, (void *)d_wout_o_, (void *)d_wout_t_,
-          (void *)d_wout_prev_})
-      if (p) (void)hipFree(p);
+    // members release themselves: buffers, then events and s_copy_, then
+    // the inner engine that lends cs_
   }
 
   int rank() const override { return rank_; }
@@ -712,7 +667,7 @@ public:
     PT_HIP_CHECK(
         hipMemcpy(d_dest_, origins, n_ * 3 * 8, hipMemcpyHostToDevice));
     const int64_t nwords = (n_ + 63) / 64;
-    unsigned long long *d_claim = pdmalloc<unsigned long long>(nwords);
+    DeviceBuffer<unsigned long long> d_claim(nwords);
     PT_HIP_CHECK(hipMemset(d_claim, 0, nwords * 8));
     PT_HIP_CHECK(hipMemset(d_ctr_, 0, 8 * 8));
     k_part_localize<<<pgrid_flat(n_), kPBlock>>>(
@@ -748,19 +703,12 @@ public:
         }
       }
       if (!cg.empty()) {
-        int32_t *d_cg = pdmalloc<int32_t>((int64_t)cg.size());
-        int32_t *d_cl = pdmalloc<int32_t>((int64_t)cl.size());
-        PT_HIP_CHECK(hipMemcpy(d_cg, cg.data(), cg.size() * 4,
-                               hipMemcpyHostToDevice));
-        PT_HIP_CHECK(hipMemcpy(d_cl, cl.data(), cl.size() * 4,
-                               hipMemcpyHostToDevice));
+        const DeviceBuffer<int32_t> d_cg = upload(cg), d_cl = upload(cl);
         k_part_apply_claims<<<pgrid((int64_t)cg.size()), kPBlock>>>(
             d_cg, d_cl, (int64_t)cg.size(), d_dest_, d_pos_, d_elem_,
             d_res_, d_esc_);
         PT_HIP_CHECK(hipGetLastError());
-        PT_HIP_CHECK(hipDeviceSynchronize());
-        PT_HIP_CHECK(hipFree(d_cg));
-        PT_HIP_CHECK(hipFree(d_cl));
+        PT_HIP_CHECK(hipDeviceSynchronize()); // before d_cg/d_cl go away
       }
     }
     PT_HIP_CHECK(hipMemcpy(d_claim, words.data(), nwords * 8,
@@ -770,8 +718,7 @@ public:
                                                 d_elem_, d_res_, d_esc_);
       PT_HIP_CHECK(hipGetLastError());
     }
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    PT_HIP_CHECK(hipFree(d_claim));
+    PT_HIP_CHECK(hipDeviceSynchronize()); // d_claim is released on return
     unsigned long long loose = 0;
     PT_HIP_CHECK(hipMemcpy(&loose, &d_ctr_[4], 8, hipMemcpyDeviceToHost));
     stats_.loose_localizations += (int64_t)loose;
@@ -784,16 +731,8 @@ public:
     PT_HIP_CHECK(hipSetDevice(device_));
     if (groups && ngroups_ <= 1)
       throw std::runtime_error("groups passed but ngroups == 1");
-    if (responses && !d_resp_) {
-      d_resp_ = pdmalloc<double>(n_ * nscores_);
-      d_wresp_ = pdmalloc<double>(n_ * nscores_);
-    }
     eng_->synchronize();
-    if (origin && !d_orig_) d_orig_ = pdmalloc<double>(n_ * 3);
-    if (groups && !d_grp_) {
-      d_grp_ = pdmalloc<uint16_t>(n_);
-      d_wgrp_ = pdmalloc<uint16_t>(n_);
-    }
+    ensure_optional(origin ? &d_orig_ : nullptr, groups, responses);
 
     // Chunked copy/walk pipeline: all chunks' H2D copies are enqueued up
     // front on the copy stream; chunk c's prepare/gather/walk on the
@@ -939,7 +878,7 @@ public:
           scounts[r] = (int64_t)dc[r];
           acc += (int64_t)dc[r];
         }
-        ensure_cap(&d_send_, &cap_send_, m * rec_w_);
+        d_send_.reserve(m * rec_w_);
         PT_HIP_CHECK(hipMemcpy(d_offs_, offs.data(), world_ * 8,
                                hipMemcpyHostToDevice));
         PT_HIP_CHECK(hipMemsetAsync(&d_ctr_[8 + world_], 0, world_ * 8,
@@ -986,7 +925,7 @@ public:
             PT_HIP_CHECK(hipMemcpy(hsend.data(), d_send_, m * rec_w_ * 8,
                                    hipMemcpyDeviceToHost));
           std::vector<double> hrecv = comm_->alltoallv(hsend.data(), sc);
-          ensure_cap(&d_recv_, &cap_recv_, (int64_t)hrecv.size());
+          d_recv_.reserve((int64_t)hrecv.size());
           if (!hrecv.empty())
             PT_HIP_CHECK(hipMemcpy(d_recv_, hrecv.data(), hrecv.size() * 8,
                                    hipMemcpyHostToDevice));
@@ -1015,7 +954,7 @@ public:
   std::vector<int64_t> resident_list() override {
     PT_HIP_CHECK(hipSetDevice(device_));
     eng_->synchronize();
-    if (!d_frame_) d_frame_ = pdmalloc<int32_t>(n_);
+    if (!d_frame_) d_frame_.allocate(n_);
     PT_HIP_CHECK(hipMemsetAsync(&d_ctr_[5], 0, 8, cs_));
     k_part_compact<<<pgrid_flat(n_), kPBlock, 0, cs_>>>(d_res_, n_, d_frame_,
                                                        &d_ctr_[5]);
@@ -1050,21 +989,13 @@ public:
       throw std::runtime_error("groups passed but ngroups == 1");
     eng_->synchronize();
     if (!d_ldest_) {
-      d_ldest_ = pdmalloc<double>(n_ * 3);
-      d_lw_ = pdmalloc<double>(n_);
-      d_lfly_ = pdmalloc<int8_t>(n_);
+      d_ldest_.allocate(n_ * 3);
+      d_lw_.allocate(n_);
+      d_lfly_.allocate(n_);
     }
-    if (origin && !d_lorig_) d_lorig_ = pdmalloc<double>(n_ * 3);
-    if (groups && !d_lgrp_) d_lgrp_ = pdmalloc<uint16_t>(n_);
-    if (responses && !d_lresp_) d_lresp_ = pdmalloc<double>(n_ * nscores_);
-    if (responses && !d_resp_) {
-      d_resp_ = pdmalloc<double>(n_ * nscores_);
-      d_wresp_ = pdmalloc<double>(n_ * nscores_);
-    }
-    if (groups && !d_grp_) {
-      d_grp_ = pdmalloc<uint16_t>(n_);
-      d_wgrp_ = pdmalloc<uint16_t>(n_);
-    }
+    if (groups && !d_lgrp_) d_lgrp_.allocate(n_);
+    if (responses && !d_lresp_) d_lresp_.allocate(n_ * nscores_);
+    ensure_optional(origin ? &d_lorig_ : nullptr, groups, responses);
     if (n_local) {
       PT_HIP_CHECK(hipMemcpy(d_ldest_, dest, n_local * 24,
                              hipMemcpyHostToDevice));
@@ -1303,11 +1234,20 @@ private:
     if (n != n_) throw std::runtime_error("global particle count mismatch");
   }
 
-  void ensure_cap(double **p, int64_t *cap, int64_t n) {
-    if (n <= *cap) return;
-    if (*p) PT_HIP_CHECK(hipFree(*p));
-    *cap = n + n / 4;
-    PT_HIP_CHECK(hipMalloc((void **)p, *cap * 8));
+  // First-use allocation of the optional step inputs, shared by step() and
+  // step_local(): the origin buffer of the calling mode (null: no origins
+  // passed), and the gid-indexed + walk-list copies of groups / responses.
+  void ensure_optional(DeviceBuffer<double> *orig, bool groups,
+                       bool responses) {
+    if (orig && !*orig) orig->allocate(n_ * 3);
+    if (responses && !d_resp_) {
+      d_resp_.allocate(n_ * nscores_);
+      d_wresp_.allocate(n_ * nscores_);
+    }
+    if (groups && !d_grp_) {
+      d_grp_.allocate(n_);
+      d_wgrp_.allocate(n_);
+    }
   }
 
   // Rare path: a resampled origin missed the local submesh grid.  The
@@ -1373,14 +1313,11 @@ private:
       }
     }
     if (!outside.empty()) {
-      int32_t *d_o = pdmalloc<int32_t>((int64_t)outside.size());
-      PT_HIP_CHECK(hipMemcpy(d_o, outside.data(), outside.size() * 4,
-                             hipMemcpyHostToDevice));
+      const DeviceBuffer<int32_t> d_o = upload(outside);
       k_part_apply_outside<<<pgrid((int64_t)outside.size()), kPBlock>>>(
           d_o, (int64_t)outside.size(), d_orig_, d_pos_, d_elem_);
       PT_HIP_CHECK(hipGetLastError());
-      PT_HIP_CHECK(hipDeviceSynchronize());
-      PT_HIP_CHECK(hipFree(d_o));
+      PT_HIP_CHECK(hipDeviceSynchronize()); // before d_o goes away
     }
   }
 
@@ -1398,47 +1335,47 @@ private:
   Decomp dec_;
   std::unique_ptr<Engine> eng_;
   Engine::DeviceMeshView dmesh_{};
-  hipStream_t cs_ = nullptr;     // the inner engine's compute stream
-  hipStream_t s_copy_ = nullptr; // step-input H2D pipeline
-  hipEvent_t ev_in_[kMaxChunks] = {};
+  // eng_ (above) lends cs_, and s_copy_ / ev_in_ order work on the buffers:
+  // all three are declared before every buffer, so they outlive them.
+  hipStream_t cs_ = nullptr; // the inner engine's compute stream
+  Stream s_copy_;            // step-input H2D pipeline
+  Event ev_in_[kMaxChunks];
   int ctr_chunk0_ = 8;
   int rec_w_ = 10;
   bool carry_grp_ = false;
-  int32_t *d_frame_ = nullptr;   // coupled-host frame (resident gids)
-  int64_t n_frame_ = -1;         // -1: no snapshot taken
-  std::vector<int64_t> h_frame_; // host copy of the frame
-  double *d_ldest_ = nullptr, *d_lw_ = nullptr, *d_lorig_ = nullptr,
-         *d_lresp_ = nullptr;
-  int8_t *d_lfly_ = nullptr;
-  uint16_t *d_lgrp_ = nullptr;
+  DeviceBuffer<int32_t> d_frame_; // coupled-host frame (resident gids)
+  int64_t n_frame_ = -1;          // -1: no snapshot taken
+  std::vector<int64_t> h_frame_;  // host copy of the frame
+  DeviceBuffer<double> d_ldest_, d_lw_, d_lorig_, d_lresp_;
+  DeviceBuffer<int8_t> d_lfly_;
+  DeviceBuffer<uint16_t> d_lgrp_;
   double loc_tol_ = 0.0;
   mutable EngineStats stats_;
 
-  int32_t *d_lowner_ = nullptr, *d_l2g_ = nullptr, *d_g2l_ = nullptr;
-  int32_t *d_fgid_ = nullptr, *d_fowner_ = nullptr;
-  double *d_pos_ = nullptr;
-  int32_t *d_elem_ = nullptr;
-  uint8_t *d_res_ = nullptr, *d_esc_ = nullptr;
-  double *d_dest_ = nullptr, *d_w_ = nullptr, *d_orig_ = nullptr;
-  double *d_resp_ = nullptr, *d_wresp_ = nullptr;
-  int8_t *d_fly_ = nullptr;
-  uint16_t *d_grp_ = nullptr, *d_wgrp_ = nullptr;
-  int32_t *d_list_ = nullptr, *d_eject_ = nullptr;
-  double *d_dep_ = nullptr;
-  unsigned long long *d_ctr_ = nullptr;
-  double *d_wpos_ = nullptr, *d_wdest_ = nullptr, *d_ww_ = nullptr;
-  int32_t *d_welem_ = nullptr, *d_wout_elem_ = nullptr;
-  double *d_wout_pos_ = nullptr, *d_wout_dest_ = nullptr;
-  double *d_dest_ovr_ = nullptr;
-  int8_t *d_wstatus_ = nullptr;
-  int64_t *d_offs_ = nullptr;
-  double *d_send_ = nullptr, *d_recv_ = nullptr;
-  int64_t cap_send_ = 0, cap_recv_ = 0;
+  DeviceBuffer<int32_t> d_lowner_, d_l2g_, d_g2l_;
+  DeviceBuffer<int32_t> d_fgid_, d_fowner_;
+  DeviceBuffer<double> d_pos_;
+  DeviceBuffer<int32_t> d_elem_;
+  DeviceBuffer<uint8_t> d_res_, d_esc_;
+  DeviceBuffer<double> d_dest_, d_w_, d_orig_;
+  DeviceBuffer<double> d_resp_, d_wresp_;
+  DeviceBuffer<int8_t> d_fly_;
+  DeviceBuffer<uint16_t> d_grp_, d_wgrp_;
+  DeviceBuffer<int32_t> d_list_, d_eject_;
+  DeviceBuffer<double> d_dep_;
+  DeviceBuffer<unsigned long long> d_ctr_;
+  DeviceBuffer<double> d_wpos_, d_wdest_, d_ww_;
+  DeviceBuffer<int32_t> d_welem_, d_wout_elem_;
+  DeviceBuffer<double> d_wout_pos_, d_wout_dest_;
+  DeviceBuffer<double> d_dest_ovr_;
+  DeviceBuffer<int8_t> d_wstatus_;
+  DeviceBuffer<int64_t> d_offs_;
+  DeviceBuffer<double> d_send_, d_recv_; // grown with reserve()
   // bitwise handoff-resume state (dep layout comment at the top)
-  double *d_t0_ = nullptr, *d_wt0_ = nullptr;
-  int32_t *d_prev_ = nullptr, *d_wprev_ = nullptr;
-  double *d_wout_o_ = nullptr, *d_wout_t_ = nullptr;
-  int32_t *d_wout_prev_ = nullptr;
+  DeviceBuffer<double> d_t0_, d_wt0_;
+  DeviceBuffer<int32_t> d_prev_, d_wprev_;
+  DeviceBuffer<double> d_wout_o_, d_wout_t_;
+  DeviceBuffer<int32_t> d_wout_prev_;
 };
 
 // ---------------------------------------------------------------------------

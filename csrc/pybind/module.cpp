@@ -633,6 +633,14 @@ PYBIND11_MODULE(_core, m) {
     }
     return out;
   });
+  // test helper: (free, total) bytes of device memory, as hipMemGetInfo
+  m.def("device_mem_info", [](int device) {
+    size_t free_b = 0, total_b = 0;
+    if (hipSetDevice(device) != hipSuccess ||
+        hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+      throw std::runtime_error("device_mem_info: hipMemGetInfo failed");
+    return py::make_tuple(free_b, total_b);
+  }, py::arg("device") = 0);
   m.def(
       "make_native_comm",
       [](bool want_gpu, int device) {

@@ -43,6 +43,7 @@ HEADERS = [
     "csrc/core/origin_delta.h",
     "csrc/comm/comm.h",
     "csrc/core/partition_engine.h",
+    "csrc/hip/hip_util.h",
     "csrc/api/PumiTally.h",
     "csrc/api/pumitally_c.h",
 ]
