@@ -17,11 +17,9 @@
 //     origin when resampling happened); walk lists are compacted on
 //     device; the walk itself is the same fused k_walk kernel as the
 //     replicated engine (walk_raw_device).
-//   * Cut-crossing particles ship as 6-double records
-//     [gid, pos x3, target global elem, group] over Comm::
-//     alltoallv_device (RCCL grouped send/recv pairs over xGMI);
-//     dest/weight are NOT shipped -- the receiver gathers them from its
-//     own uploaded global arrays by gid.
+//   * Cut-crossing particles ship as handoff records (layout:
+//     partition_record.h) over Comm::alltoallv_device (RCCL grouped
+//     send/recv pairs over xGMI).
 //   * Resampled particles (origin != committed) relocate via the LOCAL
 //     submesh grid first (covers the owned region + ghost ring); only
 //     the rare local-miss falls back to a host-side global locate.
@@ -60,9 +58,7 @@ public:
   // same global arrays.  origin == nullptr means no particle was
   // resampled (continue from committed positions).  groups optional
   // (requires ngroups > 1 at construction); responses optional
-  // (n_global * nscores score multipliers, engine.h semantics) -- like
-  // dest/weights they are gathered by gid on whichever rank walks the
-  // particle, so they never ride the exchange records.
+  // (n_global * nscores score multipliers, engine.h semantics).
   virtual void step(const double *dest, const int8_t *flying,
                     const double *weights, int64_t n_global,
                     const double *origin = nullptr,

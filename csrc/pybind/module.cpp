@@ -303,7 +303,7 @@ PYBIND11_MODULE(_core, m) {
         });
   m.def("have_gpu", &have_gpu);
 
-  // Stateful domain-decomposed engine (csrc/hip/partition_engine.hip):
+  // Stateful domain-decomposed engine (csrc/core/partition_engine.h):
   // particles stay resident on their owner rank between steps; the comm
   // (when world > 1) is the library's own TCP/RCCL layer, created from
   // the torchrun-compatible env.

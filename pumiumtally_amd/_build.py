@@ -27,6 +27,8 @@ SOURCES = [
     "csrc/core/engine_cpu.cpp",
     "csrc/core/origin_delta.cpp",
     "csrc/core/partition.cpp",
+    "csrc/core/partition_engine_common.cpp",
+    "csrc/core/partition_engine_cpu.cpp",
     "csrc/comm/comm_tcp.cpp",
     "csrc/comm/comm_rccl.hip",
     "csrc/hip/engine_gpu.hip",
@@ -43,6 +45,8 @@ HEADERS = [
     "csrc/core/origin_delta.h",
     "csrc/comm/comm.h",
     "csrc/core/partition_engine.h",
+    "csrc/core/partition_engine_common.h",
+    "csrc/core/partition_record.h",
     "csrc/hip/hip_util.h",
     "csrc/api/PumiTally.h",
     "csrc/api/pumitally_c.h",

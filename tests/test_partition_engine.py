@@ -1,5 +1,5 @@
-"""Stateful partitioned engine (csrc/hip/partition_engine.hip) vs the
-replicated single-engine oracle.
+"""Stateful partitioned engine (CPU: csrc/core/partition_engine_cpu.cpp,
+GPU: csrc/hip/partition_engine.hip) vs the replicated single-engine oracle.
 
 Residency semantics under test (matching Engine::move, engine.h):
 non-flying particles stay put; escaped particles keep clipped pos/elem
@@ -167,9 +167,9 @@ if rank == 0:
 """
 
 
-def _spawn2(tmp_path, device):
+def _spawn2(tmp_path, device, worker=None, ok="PART_ENGINE_WORLD2_OK"):
     script = tmp_path / "w.py"
-    script.write_text(WORKER)
+    script.write_text(WORKER if worker is None else worker)
     env = dict(os.environ)
     env.update({
         "WORLD_SIZE": "2",
@@ -193,7 +193,7 @@ def _spawn2(tmp_path, device):
     outs = [p.communicate(timeout=300)[0].decode() for p in procs]
     for r, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, f"rank {r} failed:\n{out}"
-    assert "PART_ENGINE_WORLD2_OK" in outs[0]
+    assert ok in outs[0]
 
 
 def test_partition_engine_world2_cpu(tmp_path):
@@ -355,6 +355,119 @@ def test_step_local_world2_cpu(tmp_path):
     for r, (p, out) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, f"rank {r} failed:\n{out}"
     assert "STEP_LOCAL_WORLD2_OK" in outs[0]
+
+
+# Coupled-host steps WITH resampled origins: the relocation branch of the
+# frame-indexed phase A and the frame-indexed eject resolver.  Shared by
+# the world-2 workers (prepended to their script) and the in-process
+# world-1 CPU-vs-GPU comparison.
+RESAMPLE_COMMON = r"""
+import numpy as np
+import pumiumtally_amd as pt
+
+RS_N, RS_STEPS, RS_SEED = 400, 4, 5
+
+
+def resample_hist():
+    rng = np.random.default_rng(RS_SEED)  # same stream on all ranks
+    pos = rng.uniform(0.05, 0.95, size=(RS_N, 3))
+    p0 = pos.copy()
+    hist = []
+    for _ in range(RS_STEPS):
+        dest = np.clip(pos + rng.normal(0, 0.3, size=(RS_N, 3)), -0.1, 1.1)
+        fly = (rng.random(RS_N) > 0.1).astype(np.int8)
+        w = rng.uniform(0.1, 1.0, RS_N)
+        res = rng.random(RS_N) < 0.10
+        origin = pos.copy()
+        origin[res] = rng.uniform(-0.05, 1.05, size=(int(res.sum()), 3))
+        hist.append((origin, dest, fly, w, res))
+        pos = np.where(fly[:, None] == 1, np.clip(dest, 0.0, 1.0), origin)
+    grp = rng.integers(0, 2, RS_N).astype(np.uint16)
+    rsp = rng.uniform(0.5, 2.0, size=(RS_N, 2))
+    return p0, hist, grp, rsp
+
+
+def resample_run(device):
+    # returns (engine, ids that left this rank in a step that resampled them)
+    p0, hist, grp, rsp = resample_hist()
+    pe = pt._core.PartitionedEngine(pt.build_box(4, 4, 4), RS_N,
+                                    device=device, ngroups=2, nscores=2)
+    pe.localize(p0.ravel())
+    moved = []
+    for origin, dest, fly, w, res in hist:
+        gids = np.asarray(pe.resident_list(), dtype=np.int64)
+        pe.step_local(dest[gids].ravel(), fly[gids], w[gids],
+                      origin=origin[gids].ravel(), groups=grp[gids],
+                      responses=rsp[gids])
+        after = np.asarray(pe.resident_mask()).astype(bool)
+        moved.extend(int(g) for g in gids if res[g] and not after[g])
+    return pe, moved
+
+
+def resample_oracle():
+    p0, hist, grp, rsp = resample_hist()
+    eng = pt.TallyEngine(pt.build_box(4, 4, 4), RS_N, device="cpu",
+                         ngroups=2, nscores=2)
+    eng.copy_initial_position(p0.ravel())
+    for origin, dest, fly, w, _ in hist:
+        eng.move(origin.ravel(), dest.ravel(), fly.copy(), w, groups=grp,
+                 responses=rsp)
+    return np.asarray(eng.flux()).ravel()
+"""
+
+RESAMPLE_WORKER = RESAMPLE_COMMON + r"""
+import os
+
+rank = int(os.environ["RANK"])
+pe, moved = resample_run(os.environ.get("PT_DEVICE", "cpu"))
+assert pe.world == int(os.environ["WORLD_SIZE"]), pe.world
+got = np.asarray(pe.flux_global())
+
+if rank == 0:
+    want = resample_oracle()
+    print("maxdiff", np.abs(got - want).max(), "relocated",
+          pe.stats()["relocated"], "moved", moved)
+    assert np.allclose(got, want, atol=1e-11), np.abs(got - want).max()
+    # the paths this test exists for were really taken
+    _, hist, _, _ = resample_hist()
+    assert any(((o[r] < 0.0) | (o[r] > 1.0)).any()
+               for o, _, _, _, r in hist), "no redrawn origin outside the box"
+    assert pe.stats()["relocated"] > 0
+    assert len(moved) > 0, "no resampled particle changed rank"
+    print("STEP_LOCAL_RESAMPLE_OK resident=", pe.resident)
+"""
+
+
+def test_step_local_resample_world2_cpu(tmp_path):
+    """Coupled-host world-2 with ~10 % of origins redrawn per step: some
+    land outside the mesh, some in the other rank's owned region, some in
+    its ghost ring.  Flux == replicated oracle."""
+    _spawn2(tmp_path, "cpu", RESAMPLE_WORKER, "STEP_LOCAL_RESAMPLE_OK")
+
+
+@pytest.mark.gpu
+def test_step_local_resample_world2_gpu_shared(tmp_path):
+    _spawn2(tmp_path, "cuda:0", RESAMPLE_WORKER, "STEP_LOCAL_RESAMPLE_OK")
+
+
+@pytest.mark.gpu
+def test_step_local_resample_world1_gpu():
+    """Same workload single-rank: the GPU engine against the CPU
+    partitioned engine.  Per-particle state involves no atomics and the
+    two walks are bitwise identical, so it compares exactly."""
+    ns = {}
+    exec(RESAMPLE_COMMON, ns)
+    cpu, _ = ns["resample_run"]("cpu")
+    gpu, _ = ns["resample_run"]("cuda:0")
+    assert gpu.stats()["relocated"] > 0
+    for name in ("positions", "elem_ids_global", "escaped_mask",
+                 "resident_mask"):
+        a = np.asarray(getattr(cpu, name)())
+        b = np.asarray(getattr(gpu, name)())
+        assert np.array_equal(a, b), name
+    fc, fg = np.asarray(cpu.flux_global()), np.asarray(gpu.flux_global())
+    print("maxdiff", np.abs(fc - fg).max())
+    assert np.allclose(fg, fc, atol=1e-11), np.abs(fc - fg).max()
 
 
 @pytest.mark.gpu

@@ -1,12 +1,13 @@
 // Address/UB-sanitizer harness over the CPU core (mesh + walk + engine +
-// partition), compiled with plain g++ (no HIP).  Runs the golden sequence
-// plus randomized fuzz through every core path.
+// partition + CPU partitioned engine), compiled with plain g++ (no HIP).
+// Runs the golden sequence plus randomized fuzz through every core path.
 // Build/run: tools/asan_check.sh
 #include "../csrc/comm/comm.h"
 
 #include <sys/wait.h>
 #include <unistd.h>
 #include "../csrc/core/engine.h"
+#include "../cpp/partition_cpu_scenario.h"
 
 #include <cassert>
 #include <cmath>
@@ -154,6 +155,9 @@ int main() {
   golden();
   fuzz();
   threaded_scored_move();
+  // the CPU stateful partitioned engine: step() and step_local() with
+  // resampled origins, against the replicated engine
+  if (partition_cpu_scenario() != 0) abort();
   comm_world2();
   printf("asan_check: PASS\n");
   return 0;
