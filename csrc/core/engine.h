@@ -202,6 +202,28 @@ public:
   // all-reduced global tally on rank 0 before writing).
   virtual void set_flux(const double *flux, int64_t nelems) = 0;
 
+  // Linear (per-vertex) track-length moments -- only on engines created
+  // with linear=true; every call below throws otherwise.  For each tallied
+  // crossing the walk adds, next to the flux contribution, the 4 first
+  // barycentric moments  m_f = integral of weight * lambda_f dl  over the
+  // chord (walk.h tet_moments), with groups and scores applied exactly as
+  // for flux.  Layout: [nscores x ngroups x nelems x 4], local vertex
+  // fastest (a crossing's four adds are one 32-byte span).  sum_f m_f equals
+  // the flux entry up to rounding.  The flux tally itself is produced
+  // exactly as without linear mode.
+  // end_batch() adds the per-batch moments into a running sum
+  // (moment_sum) and zeroes them.  Moments get NO sum of squares: their
+  // consumers reconstruct a field from the batch-summed moments, and a
+  // variance of the derived nodal values is not a per-entry quantity.
+  virtual std::vector<double> moments() const { throw_not_linear(); }
+  virtual std::vector<double> moment_sum() const { throw_not_linear(); }
+  // Overwrite the per-batch moments (checkpoint restore); n must be the
+  // full moments size.
+  virtual void set_moments(const double *m, int64_t n) {
+    (void)m; (void)n;
+    throw_not_linear();
+  }
+
   // Restore particle state (checkpoint/resume support -- the reference has
   // none; a crash there loses the whole batch).
   virtual void set_particle_state(const double *pos, const int32_t *elem,
@@ -233,6 +255,10 @@ public:
 
   bool reflective = false; // specular-reflect at boundaries (else vacuum)
 
+  // Linear moment tallies enabled (see moments()).  Fixed at construction
+  // (make_*_engine's trailing argument); read-only afterwards.
+  bool linear = false;
+
   // fp32-traversal fast path (walk.h walk_advance32): candidate exit-face
   // decisions in fp32, crossings/tallies in fp64.  Controlled by
   // PUMITALLY_WALK=fp32|fp64; both engines honor it so CPU remains the
@@ -250,6 +276,12 @@ public:
   bool origin_elide = true;
   int origin_threads = 8;
   int64_t origin_chunk = 0;
+
+protected:
+  [[noreturn]] static void throw_not_linear() {
+    throw std::runtime_error(
+        "linear moment tallies are off: create the engine with linear=true");
+  }
 };
 
 inline bool default_walk_fp32() {
@@ -292,12 +324,13 @@ inline double loc_tol_rel() {
 }
 
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
-                                        int ngroups = 1, int nscores = 1);
+                                        int ngroups = 1, int nscores = 1,
+                                        bool linear = false);
 
 // Returns nullptr when no HIP device is available.
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
                                         int device, int ngroups = 1,
-                                        int nscores = 1);
+                                        int nscores = 1, bool linear = false);
 
 // Normalized flux = flux / element volume (volume-only, matching the
 // reference implementation rather than its docstring:

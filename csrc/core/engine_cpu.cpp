@@ -30,11 +30,16 @@ namespace {
 
 class CpuEngine final : public Engine {
 public:
-  CpuEngine(Mesh mesh, int64_t n, int groups, int scores)
+  CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
+    linear = lin;
     flux_.assign(mesh_.nelems * ngroups * nscores, 0.0);
+    if (linear) {
+      mesh_.build_inv_heights();
+      moments_.assign(flux_.size() * 4, 0.0);
+    }
     pos_.resize(n_ * 3);
     elem_.assign(n_, 0);
     escaped_.assign(n_, 0);
@@ -108,6 +113,10 @@ public:
       // tools/part_world2_soak at 400k particles with nscores=2)
       std::vector<std::vector<double>> partial(
           nthreads, std::vector<double>(flux_.size(), 0.0));
+      // ... and, in linear mode, a moments partial of the full moments
+      // shape (4x the flux shape; empty otherwise, never written then)
+      std::vector<std::vector<double>> partial_m(
+          nthreads, std::vector<double>(moments_.size(), 0.0));
       std::atomic<int64_t> lost{0}, reloc{0};
       std::vector<std::thread> workers;
       const int64_t per = (n + nthreads - 1) / nthreads;
@@ -117,7 +126,8 @@ public:
           int64_t my_lost = 0, my_reloc = 0;
           for (int64_t i = lo; i < hi; ++i)
             move_one(origin, dest, flying, weights, groups, responses, i,
-                     steps, partial[t].data(), my_lost, my_reloc);
+                     steps, partial[t].data(), partial_m[t].data(), my_lost,
+                     my_reloc);
           lost += my_lost;
           reloc += my_reloc;
         });
@@ -126,6 +136,9 @@ public:
       for (int t = 0; t < nthreads; ++t)
         for (size_t e = 0; e < flux_.size(); ++e)
           flux_[e] += partial[t][e];
+      for (int t = 0; t < nthreads; ++t)
+        for (size_t e = 0; e < moments_.size(); ++e)
+          moments_[e] += partial_m[t][e];
       stats_.lost_particles += lost.load();
       stats_.relocated += reloc.load();
       stats_.moves++;
@@ -134,7 +147,7 @@ public:
     int64_t lost = 0, reloc = 0;
     for (int64_t i = 0; i < n; ++i)
       move_one(origin, dest, flying, weights, groups, responses, i, steps,
-               flux_.data(), lost, reloc);
+               flux_.data(), moments_.data(), lost, reloc);
     stats_.lost_particles += lost;
     stats_.relocated += reloc;
     stats_.moves++;
@@ -145,7 +158,8 @@ public:
   void move_one(const double *origin, const double *dest,
                 const int8_t *flying, const double *weights,
                 const uint16_t *groups, const double *responses, int64_t i,
-                int steps, double *flux_out, int64_t &lost, int64_t &reloc) {
+                int steps, double *flux_out, double *mom_out, int64_t &lost,
+                int64_t &reloc) {
     if (!flying[i]) return;
     Vec3 o{pos_[i * 3], pos_[i * 3 + 1], pos_[i * 3 + 2]};
     if (origin && !escaped_[i]) {
@@ -185,18 +199,28 @@ public:
         mesh_.face_bc_bits.empty() ? nullptr : mesh_.face_bc_bits.data();
     const int32_t *pix =
         mesh_.periodic_idx.empty() ? nullptr : mesh_.periodic_idx.data();
-    if (walk_fp32)
-      walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
-                           mesh_.nbr.data(), elem_[i], o, d, weights[i],
-                           steps, add, &out_elem, &out_pos, &out_esc,
-                           reflective, bc, pix, mesh_.periodic_elem.data(),
+    auto walk = [&](auto &tally) {
+      if (walk_fp32)
+        walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
+                             mesh_.nbr.data(), elem_[i], o, d, weights[i],
+                             steps, tally, &out_elem, &out_pos, &out_esc,
+                             reflective, bc, pix, mesh_.periodic_elem.data(),
+                             mesh_.periodic_shift.data());
+      else
+        walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem_[i], o,
+                           d, weights[i], steps, tally, &out_elem, &out_pos,
+                           &out_esc, reflective, bc, pix,
+                           mesh_.periodic_elem.data(),
                            mesh_.periodic_shift.data());
-    else
-      walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem_[i], o,
-                         d, weights[i], steps, add, &out_elem, &out_pos,
-                         &out_esc, reflective, bc, pix,
-                         mesh_.periodic_elem.data(),
-                         mesh_.periodic_shift.data());
+    };
+    if (linear) {
+      auto add_lin = [&](int32_t e, double t0, double t1, const WalkState &s) {
+        add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
+      };
+      walk(add_lin);
+    } else {
+      walk(add);
+    }
     if (out_elem == kWalkLost) {
       lost++;
       record_lost(i, out_pos);
@@ -225,6 +249,8 @@ public:
       const int nthreads = (int)std::min<unsigned>(hw, 64);
       std::vector<std::vector<double>> partial(
           nthreads, std::vector<double>(flux_.size(), 0.0));
+      std::vector<std::vector<double>> partial_m(
+          nthreads, std::vector<double>(moments_.size(), 0.0));
       std::atomic<int64_t> lost{0};
       std::vector<std::thread> workers;
       const int64_t per = (n + nthreads - 1) / nthreads;
@@ -236,13 +262,16 @@ public:
             walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
                          out_elem, out_status, out_dest, in_t, in_prev,
                          out_o, out_t, out_prev, i, steps,
-                         partial[t].data(), my_lost);
+                         partial[t].data(), partial_m[t].data(), my_lost);
           lost += my_lost;
         });
       }
       for (auto &w : workers) w.join();
       for (int t = 0; t < nthreads; ++t)
         for (size_t e = 0; e < flux_.size(); ++e) flux_[e] += partial[t][e];
+      for (int t = 0; t < nthreads; ++t)
+        for (size_t e = 0; e < moments_.size(); ++e)
+          moments_[e] += partial_m[t][e];
       stats_.lost_particles += lost.load();
       return;
     }
@@ -250,7 +279,8 @@ public:
     for (int64_t i = 0; i < n; ++i)
       walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
                    out_elem, out_status, out_dest, in_t, in_prev, out_o,
-                   out_t, out_prev, i, steps, flux_.data(), lost);
+                   out_t, out_prev, i, steps, flux_.data(), moments_.data(),
+                   lost);
     stats_.lost_particles += lost;
   }
 
@@ -261,7 +291,7 @@ public:
                     double *out_dest, const double *in_t,
                     const int32_t *in_prev, double *out_o, double *out_t,
                     int32_t *out_prev, int64_t i, int steps,
-                    double *flux_out, int64_t &lost) {
+                    double *flux_out, double *mom_out, int64_t &lost) {
     {
       const Vec3 o{pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]};
       const Vec3 d{dest[i * 3], dest[i * 3 + 1], dest[i * 3 + 2]};
@@ -290,19 +320,34 @@ public:
       Vec3 oo{o.x, o.y, o.z};
       double ot = 0.0;
       int32_t opv = -1;
-      if (walk_fp32)
-        walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
-                             mesh_.nbr.data(), elem[i], o, d, weights[i],
-                             steps, add, &oe, &op, &esc, reflective, bc, pix,
-                             mesh_.periodic_elem.data(),
+      // Resumed walks (in_t / in_prev) need nothing extra for the moments:
+      // in_t only seeds t_cur, pos is the wrap-segment origin the sender
+      // exported, so (o, d, seg_len) -- all tet_moments reads besides
+      // [t0, t1] -- are the uncut walk's.
+      auto walk = [&](auto &tally) {
+        if (walk_fp32)
+          walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
+                               mesh_.nbr.data(), elem[i], o, d, weights[i],
+                               steps, tally, &oe, &op, &esc, reflective, bc,
+                               pix, mesh_.periodic_elem.data(),
+                               mesh_.periodic_shift.data(), &od, rt, rp, &oo,
+                               &ot, &opv);
+        else
+          walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem[i],
+                             o, d, weights[i], steps, tally, &oe, &op, &esc,
+                             reflective, bc, pix, mesh_.periodic_elem.data(),
                              mesh_.periodic_shift.data(), &od, rt, rp, &oo,
                              &ot, &opv);
-      else
-        walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem[i], o,
-                           d, weights[i], steps, add, &oe, &op, &esc,
-                           reflective, bc, pix, mesh_.periodic_elem.data(),
-                           mesh_.periodic_shift.data(), &od, rt, rp, &oo,
-                           &ot, &opv);
+      };
+      if (linear) {
+        auto add_lin = [&](int32_t e, double t0, double t1,
+                           const WalkState &s) {
+          add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
+        };
+        walk(add_lin);
+      } else {
+        walk(add);
+      }
       int8_t st = 0;
       if (oe == kWalkLost) {
         st = 3;
@@ -344,6 +389,13 @@ public:
       batch_sq_[e] += flux_[e] * flux_[e];
       flux_[e] = 0.0;
     }
+    if (linear) {
+      if (moment_sum_.empty()) moment_sum_.assign(moments_.size(), 0.0);
+      for (size_t e = 0; e < moments_.size(); ++e) {
+        moment_sum_[e] += moments_[e];
+        moments_[e] = 0.0;
+      }
+    }
     nbatches_++;
   }
   std::vector<double> batch_sum() const override {
@@ -374,6 +426,22 @@ public:
     std::memcpy(flux_.data(), f, ne * sizeof(double));
   }
 
+  std::vector<double> moments() const override {
+    if (!linear) throw_not_linear();
+    return moments_;
+  }
+  std::vector<double> moment_sum() const override {
+    if (!linear) throw_not_linear();
+    return moment_sum_.empty() ? std::vector<double>(moments_.size(), 0.0)
+                               : moment_sum_;
+  }
+  void set_moments(const double *m, int64_t n) override {
+    if (!linear) throw_not_linear();
+    if (n != (int64_t)moments_.size())
+      throw std::runtime_error("set_moments size mismatch");
+    std::memcpy(moments_.data(), m, n * sizeof(double));
+  }
+
   void set_particle_state(const double *pos, const int32_t *elem,
                           const uint8_t *escaped, int64_t n) override {
     check_n(n);
@@ -385,6 +453,29 @@ public:
 private:
   void check_n(int64_t n) const {
     if (n != n_) throw std::runtime_error("particle count mismatch");
+  }
+
+  // Linear-mode contribution (rich walk callback): the flux add is the
+  // plain path's expression and order, so flux stays bit-identical to a
+  // non-linear engine's; the 4 moments land next to each other at
+  // (flux index)*4.
+  void add_linear(double *flux_out, double *mom_out, int64_t goff,
+                  int64_t gsz, const double *resp, int32_t e, double t0,
+                  double t1, const WalkState &s) const {
+    const double v = (t1 - t0) * s.seg_len * s.weight;
+    double m[4];
+    tet_moments(mesh_.planes.data() + (int64_t)e * 4,
+                mesh_.inv_heights.data() + (int64_t)e * 4, s, t0, t1, v, m);
+    if (!resp) {
+      flux_out[goff + e] += v;
+      for (int f = 0; f < 4; ++f) mom_out[(goff + e) * 4 + f] += m[f];
+      return;
+    }
+    for (int k = 0; k < nscores; ++k) {
+      flux_out[k * gsz + goff + e] += v * resp[k];
+      for (int f = 0; f < 4; ++f)
+        mom_out[(k * gsz + goff + e) * 4 + f] += m[f] * resp[k];
+    }
   }
 
   void record_lost(int64_t i, Vec3 p) {
@@ -401,6 +492,7 @@ private:
   int64_t n_;
   double loc_tol_;
   std::vector<double> flux_, pos_, batch_sum_, batch_sq_;
+  std::vector<double> moments_, moment_sum_; // linear mode only, else empty
   int64_t nbatches_ = 0;
   std::vector<int32_t> elem_;
   std::vector<uint8_t> escaped_;
@@ -414,9 +506,10 @@ private:
 } // namespace
 
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
-                                        int ngroups, int nscores) {
+                                        int ngroups, int nscores,
+                                        bool linear) {
   return std::make_unique<CpuEngine>(std::move(mesh), num_particles, ngroups,
-                                     nscores);
+                                     nscores, linear);
 }
 
 } // namespace pumitally

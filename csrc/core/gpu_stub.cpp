@@ -9,7 +9,7 @@
 
 namespace pumitally {
 
-std::unique_ptr<Engine> make_gpu_engine(Mesh, int64_t, int, int, int) {
+std::unique_ptr<Engine> make_gpu_engine(Mesh, int64_t, int, int, int, bool) {
   return nullptr;
 }
 

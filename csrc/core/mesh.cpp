@@ -90,6 +90,14 @@ void Mesh::set_periodic_faces(const std::vector<int64_t> &faces_a,
   }
 }
 
+void Mesh::build_inv_heights() {
+  if (planes.size() != (size_t)nelems * 4)
+    throw std::runtime_error("build_inv_heights: call finalize() first");
+  inv_heights.resize((size_t)nelems * 4);
+  for (int64_t i = 0; i < nelems * 4; ++i)
+    inv_heights[i] = 1.0 / plane_eval(planes[i], vert(tet2vert[i]));
+}
+
 bool Mesh::contains(int32_t t, Vec3 p, double tol) const {
   for (int f = 0; f < 4; ++f)
     if (plane_eval(planes[t * 4 + f], p) < -tol) return false;

@@ -88,6 +88,14 @@ struct Mesh {
   Vec3 bbox_lo{0, 0, 0}, bbox_hi{0, 0, 0};
   LocGrid grid;
 
+  // nelems*4: 1 / h_f, h_f = height of local vertex f above local face f
+  // (= plane_eval(planes[4e+f], vertex tet2vert[4e+f])), so the barycentric
+  // coordinate of vertex f is plane_eval(planes[4e+f], p) * inv_heights[4e+f].
+  // NOT built by finalize(): only the linear-moment engines need it and
+  // call build_inv_heights() on their own mesh copy.
+  std::vector<double> inv_heights;
+  void build_inv_heights();
+
   // Build adjacency, planes, volumes, bbox and the localization grid.
   // Reorients negatively-oriented tets in place (swaps verts 2,3).
   void finalize();
@@ -167,9 +175,12 @@ Mesh read_gmsh(const std::string &path);             // Gmsh .msh v2.2/v4.1 ASCI
 Mesh read_mesh(const std::string &path);             // dispatch on extension
 // binary: 1 = legacy binary (big-endian), 0 = ASCII, -1 = auto (binary for
 // meshes over 200k elements -- ~10x smaller/faster finalization).
+// point_data (optional): per-vertex fields (nverts doubles each); with none
+// given the file is byte-for-byte what it was before point data existed.
 void write_vtk(const std::string &path, const Mesh &m,
                const std::vector<std::pair<std::string, std::vector<double>>> &cell_data,
-               int binary = -1);
+               int binary = -1,
+               const std::vector<std::pair<std::string, std::vector<double>>> &point_data = {});
 Mesh read_osh(const std::string &dir);               // .osh directory
 void write_osh(const std::string &dir, const Mesh &m);
 

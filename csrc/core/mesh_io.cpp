@@ -44,7 +44,8 @@ void swap_write_i32(std::ofstream &f, const int32_t *v, int64_t n) {
 // directories (vtk::write_parallel, PumiTallyImpl.cpp:415); a single .vtu
 // covers the rank-0-gathered output this framework produces.
 static void write_vtu(const std::string &path, const Mesh &m,
-                      const std::vector<std::pair<std::string, std::vector<double>>> &cell_data) {
+                      const std::vector<std::pair<std::string, std::vector<double>>> &cell_data,
+                      const std::vector<std::pair<std::string, std::vector<double>>> &point_data) {
   // The appended blocks are raw host memory declared LittleEndian in the
   // header; on a big-endian host that would silently corrupt the file
   // (the legacy .vtk path byte-swaps; this one does not), so refuse.
@@ -57,7 +58,8 @@ static void write_vtu(const std::string &path, const Mesh &m,
   }
   std::ofstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("cannot open " + path + " for writing");
-  // appended blocks: points, connectivity, offsets, types, then cell data
+  // appended blocks: points, connectivity, offsets, types, then cell data,
+  // then point data (if any)
   uint64_t off = 0;
   const uint64_t b_points = m.nverts * 3 * 8;
   const uint64_t b_conn = m.nelems * 4 * 8;
@@ -73,6 +75,7 @@ static void write_vtu(const std::string &path, const Mesh &m,
   next(b_offs);
   next(b_types);
   for (const auto &cd : cell_data) next((uint64_t)cd.second.size() * 8);
+  for (const auto &pd : point_data) next((uint64_t)pd.second.size() * 8);
 
   f << "<?xml version=\"1.0\"?>\n"
     << "<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" "
@@ -95,7 +98,15 @@ static void write_vtu(const std::string &path, const Mesh &m,
   for (const auto &cd : cell_data)
     f << "<DataArray type=\"Float64\" Name=\"" << cd.first
       << "\" format=\"appended\" offset=\"" << offsets[bi++] << "\"/>\n";
-  f << "</CellData>\n</Piece>\n</UnstructuredGrid>\n"
+  f << "</CellData>\n";
+  if (!point_data.empty()) {
+    f << "<PointData>\n";
+    for (const auto &pd : point_data)
+      f << "<DataArray type=\"Float64\" Name=\"" << pd.first
+        << "\" format=\"appended\" offset=\"" << offsets[bi++] << "\"/>\n";
+    f << "</PointData>\n";
+  }
+  f << "</Piece>\n</UnstructuredGrid>\n"
     << "<AppendedData encoding=\"raw\">_";
   auto block = [&](const void *data, uint64_t bytes) {
     f.write((const char *)&bytes, 8);
@@ -118,15 +129,22 @@ static void write_vtu(const std::string &path, const Mesh &m,
   }
   for (const auto &cd : cell_data)
     block(cd.second.data(), (uint64_t)cd.second.size() * 8);
+  for (const auto &pd : point_data)
+    block(pd.second.data(), (uint64_t)pd.second.size() * 8);
   f << "</AppendedData>\n</VTKFile>\n";
   if (!f) throw std::runtime_error("write failed: " + path);
 }
 
 void write_vtk(const std::string &path, const Mesh &m,
                const std::vector<std::pair<std::string, std::vector<double>>> &cell_data,
-               int binary /* -1 = auto (binary for big meshes) */) {
+               int binary /* -1 = auto (binary for big meshes) */,
+               const std::vector<std::pair<std::string, std::vector<double>>> &point_data) {
+  for (const auto &pd : point_data)
+    if ((int64_t)pd.second.size() != m.nverts)
+      throw std::runtime_error("write_vtk: point field '" + pd.first +
+                               "' must have nverts values");
   if (path.size() > 4 && path.compare(path.size() - 4, 4, ".vtu") == 0)
-    return write_vtu(path, m, cell_data);
+    return write_vtu(path, m, cell_data, point_data);
   const bool bin = binary < 0 ? m.nelems > 200000 : binary != 0;
   std::ofstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("cannot open " + path + " for writing");
@@ -179,6 +197,21 @@ void write_vtk(const std::string &path, const Mesh &m,
       } else {
         for (int64_t t = 0; t < m.nelems; ++t) {
           snprintf(buf, sizeof buf, "%.17g\n", cd.second[t]);
+          f << buf;
+        }
+      }
+    }
+  }
+  if (!point_data.empty()) {
+    f << "POINT_DATA " << m.nverts << "\n";
+    for (const auto &pd : point_data) {
+      f << "SCALARS " << pd.first << " double 1\nLOOKUP_TABLE default\n";
+      if (bin) {
+        swap_write_f64(f, pd.second.data(), m.nverts);
+        f << "\n";
+      } else {
+        for (int64_t v = 0; v < m.nverts; ++v) {
+          snprintf(buf, sizeof buf, "%.17g\n", pd.second[v]);
           f << buf;
         }
       }

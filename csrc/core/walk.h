@@ -23,6 +23,8 @@
 
 #include "geom.h"
 
+#include <type_traits>
+
 namespace pumitally {
 
 constexpr double kWalkTEps = 1e-12;   // tolerance on the segment parameter t
@@ -70,7 +72,8 @@ PT_HD void walk_init(WalkState &s, int32_t elem, Vec3 o, Vec3 d, double w) {
 }
 
 // Advance one element crossing.  Returns true when the walk finished and
-// the out_* values are valid.  FluxAdd: void(int32_t elem, double v).
+// the out_* values are valid.  FluxAdd: void(int32_t elem, double v), or the
+// rich form described at walk_contribute.
 // Specular reflection of point p across plane pl (unit normal).
 PT_HD Vec3 reflect_point(const Plane &pl, Vec3 p) {
   const double v = plane_eval(pl, p);
@@ -96,6 +99,54 @@ PT_HD void periodic_restart(WalkState &s, double t_clamped,
   s.elem = pair_elem;
   s.step = 0; // fresh per-wrap budget; total wraps capped by kMaxWraps
   s.wraps++;
+}
+
+// Contribution hook shared by every tally site of both advance variants
+// (the final partial segment, and the crossing taken before stepping to the
+// neighbor / a boundary clip / a handoff / a reflective or periodic
+// restart).  The crossing covers the segment parameter range
+// [s.t_cur, t1] of the walk state's CURRENT (o, d, seg_len, weight); it is
+// always called before a restart rebases them.  Two callback forms:
+//   legacy  void(int32_t elem, double length_times_weight)
+//   rich    void(int32_t elem, double t0, double t1, const WalkState &)
+// The rich form additionally sees the entry/exit parameters and the walk
+// state (the linear moment tallies need the chord's end points, see
+// tet_moments).  The legacy form receives exactly the expression it always
+// did, so plain flux tallies are bit-for-bit unchanged.
+template <class FluxAdd>
+PT_HD void walk_contribute(FluxAdd &add, const WalkState &s, double t1) {
+  if constexpr (std::is_invocable_v<FluxAdd &, int32_t, double, double,
+                                    const WalkState &>)
+    add(s.elem, s.t_cur, t1, s);
+  else
+    add(s.elem, (t1 - s.t_cur) * s.seg_len * s.weight);
+}
+
+// First barycentric moments of one crossing: m[f] = integral over the chord
+// [t0, t1] of weight * lambda_f dl, for the 4 local vertices f of the tet
+// whose planes are pl[0..3].  Local face f is opposite local vertex f and
+// planes are inward-positive unit normals, so lambda_f(p) =
+// plane_eval(pl[f], p) * inv_h[f] (inv_h = 1 / height of vertex f above
+// face f, Mesh::inv_heights).  lambda_f is linear along the segment, so the
+// midpoint rule is exact:
+//   m[f] = len_w * (vo_f + 0.5*(t0+t1) * (vd_f - vo_f)) * inv_h[f]
+// with len_w = (t1-t0)*seg_len*weight -- the very value the flux tally gets,
+// so sum_f m[f] == len_w up to rounding (partition of unity).  Always fp64
+// from the fp64 planes, also under fp32 traversal.  ONE fixed evaluation
+// order (and the build's -ffp-contract=off) keeps every per-contribution
+// value bit-identical between the CPU oracle and the HIP kernels.
+PT_HD void tet_moments(const Plane *__restrict__ pl,
+                       const double *__restrict__ inv_h, const WalkState &s,
+                       double t0, double t1, double len_w, double m[4]) {
+  const double tm = 0.5 * (t0 + t1);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int f = 0; f < 4; ++f) {
+    const double vo = plane_eval(pl[f], s.o);
+    const double vd = plane_eval(pl[f], s.d);
+    m[f] = len_w * (vo + tm * (vd - vo)) * inv_h[f];
+  }
 }
 
 // Periodic=false (the default, and the headline GPU instantiation) compiles
@@ -159,7 +210,7 @@ PT_HD bool walk_advance(const Plane *__restrict__ planes,
   if (exit_face < 0 || t_exit >= 1.0) {
     // Destination lies inside this element: tally the final partial
     // segment and stop (reference: reached_destination, last_exit==-1).
-    if (s.tally) add(s.elem, (1.0 - s.t_cur) * s.seg_len * s.weight);
+    if (s.tally) walk_contribute(add, s, 1.0);
     *out_elem = s.elem;
     *out_pos = s.d;
     *out_escaped = false;
@@ -167,7 +218,7 @@ PT_HD bool walk_advance(const Plane *__restrict__ planes,
   }
 
   const double t_clamped = t_exit > s.t_cur ? t_exit : s.t_cur;
-  if (s.tally) add(s.elem, (t_clamped - s.t_cur) * s.seg_len * s.weight);
+  if (s.tally) walk_contribute(add, s, t_clamped);
 
   const int32_t next = nbr[(int64_t)s.elem * 4 + exit_face];
   if (next == -1) {
@@ -284,7 +335,7 @@ PT_HD bool walk_advance32(const Plane *__restrict__ planes,
   }
 
   if (exit_face < 0 || t_exit >= 1.0f) {
-    if (s.tally) add(s.elem, (1.0 - s.t_cur) * s.seg_len * s.weight);
+    if (s.tally) walk_contribute(add, s, 1.0);
     *out_elem = s.elem;
     *out_pos = s.d;
     *out_escaped = false;
@@ -298,7 +349,7 @@ PT_HD bool walk_advance32(const Plane *__restrict__ planes,
   double t64 = (vo64 - vd64) > 0.0 ? vo64 / (vo64 - vd64) : s.t_cur;
   if (t64 > 1.0) t64 = 1.0;
   const double t_clamped = t64 > s.t_cur ? t64 : s.t_cur;
-  if (s.tally) add(s.elem, (t_clamped - s.t_cur) * s.seg_len * s.weight);
+  if (s.tally) walk_contribute(add, s, t_clamped);
 
   const int32_t next = nbr[(int64_t)s.elem * 4 + exit_face];
   if (next == -1) {

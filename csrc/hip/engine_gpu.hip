@@ -201,6 +201,16 @@ __global__ void k_accumulate_batch(double *__restrict__ flux,
   }
 }
 
+// end_batch() pass over the linear moments: running sum, then zero.
+__global__ void k_accumulate_moments(double *__restrict__ mom,
+                                     double *__restrict__ msum, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    msum[i] += mom[i];
+    mom[i] = 0.0;
+  }
+}
+
 __global__ void k_reduce_slices(double *__restrict__ flux, int64_t nelems,
                                 int slices) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -252,6 +262,48 @@ __device__ __forceinline__ void wave_agg_atomic_add(double *__restrict__ flux,
   if (!next_active || next_el != el) atomicAdd(&flux[el], acc);
 }
 
+// Linear-mode form of the above: the run structure (heads, tails) depends
+// only on el and the active mask, so it is computed ONCE and the segmented
+// sum is run over five values -- the flux contribution and the crossing's
+// four moments.  The run tail issues one atomic per component: flux[el]
+// and the 32-byte span moments[4*el .. 4*el+3].  (How the memory side
+// treats a 32-byte atomic span is unmeasured; nothing here relies on it.)
+__device__ __forceinline__ void
+wave_agg_atomic_add_linear(double *__restrict__ flux,
+                           double *__restrict__ moments, int32_t el, double v,
+                           const double (&m)[4]) {
+  const unsigned long long mask = __ballot(1);
+  const int lane = (int)(threadIdx.x & 63u);
+  const int32_t prev_el = __shfl_up(el, 1);
+  const bool prev_active = lane > 0 && ((mask >> (lane - 1)) & 1ull);
+  const bool head = !prev_active || prev_el != el;
+  int head_lane = head ? lane : 0;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int up = __shfl_up(head_lane, off);
+    if (lane >= off && ((mask >> (lane - off)) & 1ull) && up > head_lane)
+      head_lane = up;
+  }
+  double acc[5] = {v, m[0], m[1], m[2], m[3]};
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const bool take = lane - off >= head_lane;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+      const double up = __shfl_up(acc[c], off);
+      if (take) acc[c] += up;
+    }
+  }
+  const int32_t next_el = __shfl_down(el, 1);
+  const bool next_active = lane < 63 && ((mask >> (lane + 1)) & 1ull);
+  if (!next_active || next_el != el) {
+    atomicAdd(&flux[el], acc[0]);
+    double *mo = moments + (int64_t)el * 4;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) atomicAdd(&mo[f], acc[1 + f]);
+  }
+}
+
 inline bool wave_agg() {
   static bool v = [] {
     const char *s = getenv("PUMITALLY_WAVE_AGG");
@@ -270,8 +322,13 @@ inline bool wave_agg() {
 // dispatches block b to XCD b%8 and each XCD has a private 4 MiB L2; we
 // remap blocks so each XCD owns one contiguous (hence spatially compact)
 // slot range.  Purely a speed lever: any placement is correct.
+//
+// Linear=true additionally tallies the crossing's four barycentric moments
+// (walk.h tet_moments) into `moments` -- ONE un-sliced array, see
+// flux_slices -- reading `inv_h`.  Linear=false instantiations never read
+// either trailing argument.
 template <bool F32, bool Scored = false, bool Periodic = false,
-          bool Agg = false>
+          bool Agg = false, bool Linear = false>
 __global__ void k_move(const Plane *__restrict__ planes,
                        const Plane32 *__restrict__ planes32,
                        const int32_t *__restrict__ nbr, GridView grid,
@@ -294,7 +351,9 @@ __global__ void k_move(const Plane *__restrict__ planes,
                        int nscores = 1,
                        const int32_t *__restrict__ pidx = nullptr,
                        const int32_t *__restrict__ pelem = nullptr,
-                       const double *__restrict__ pshift = nullptr) {
+                       const double *__restrict__ pshift = nullptr,
+                       const double *__restrict__ inv_h = nullptr,
+                       double *__restrict__ moments = nullptr) {
   // Scored=false, Periodic=false is the headline instantiation:
   // resp/nscores/pidx are unused, the slice stride stays nelems*ngroups,
   // and the walk compiles without the score loop or the periodic branch --
@@ -352,14 +411,50 @@ __global__ void k_move(const Plane *__restrict__ planes,
         atomicAdd(&flux[goff + el], v);
       }
     };
-    if constexpr (F32)
-      walk_segment32<Periodic>(planes, planes32, nbr, e, o, d, weights[c],
-                               max_steps, add, &out_elem, &out_pos, &out_esc,
+    // Linear-mode contribution (rich walk callback).  The flux value is the
+    // plain path's expression; moments index = (flux index)*4 + vertex.
+    auto add_lin = [&](int32_t el, double t0, double t1, const WalkState &s) {
+      const double v = (t1 - t0) * s.seg_len * s.weight;
+      double m[4];
+      tet_moments(planes + (int64_t)el * 4, inv_h + (int64_t)el * 4, s, t0,
+                  t1, v, m);
+      if constexpr (Scored) {
+        const int64_t gsz = (int64_t)ngroups * nelems;
+        if (resp) {
+          for (int k = 0; k < nscores; ++k) {
+            const double r = resp[c * nscores + k];
+            const int64_t at = k * gsz + goff + el;
+            atomicAdd(&flux[at], v * r);
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+              atomicAdd(&moments[at * 4 + f], m[f] * r);
+          }
+          return;
+        }
+      } else if constexpr (Agg) {
+        wave_agg_atomic_add_linear(flux, moments, el, v, m);
+        return;
+      }
+      atomicAdd(&flux[goff + el], v);
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+        atomicAdd(&moments[(goff + el) * 4 + f], m[f]);
+    };
+    auto walk = [&](auto &tally) {
+      if constexpr (F32)
+        walk_segment32<Periodic>(planes, planes32, nbr, e, o, d, weights[c],
+                                 max_steps, tally, &out_elem, &out_pos,
+                                 &out_esc, reflective, face_bc, pidx, pelem,
+                                 pshift);
+      else
+        walk_segment<Periodic>(planes, nbr, e, o, d, weights[c], max_steps,
+                               tally, &out_elem, &out_pos, &out_esc,
                                reflective, face_bc, pidx, pelem, pshift);
+    };
+    if constexpr (Linear)
+      walk(add_lin);
     else
-      walk_segment<Periodic>(planes, nbr, e, o, d, weights[c], max_steps,
-                             add, &out_elem, &out_pos, &out_esc, reflective,
-                             face_bc, pidx, pelem, pshift);
+      walk(add);
     if (out_elem == kWalkLost) {
       const unsigned long long k = atomicAdd(lost, 1ull);
       if (k < (unsigned long long)kMaxLostRecords) {
@@ -378,7 +473,7 @@ __global__ void k_move(const Plane *__restrict__ planes,
   }
 }
 
-template <bool F32>
+template <bool F32, bool Linear = false>
 __global__ void k_walk_raw(const Plane *__restrict__ planes,
                            const Plane32 *__restrict__ planes32,
                            const int32_t *__restrict__ nbr,
@@ -405,7 +500,9 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
                            const int32_t *__restrict__ in_prev = nullptr,
                            double *__restrict__ out_o = nullptr,
                            double *__restrict__ out_t = nullptr,
-                           int32_t *__restrict__ out_prev = nullptr) {
+                           int32_t *__restrict__ out_prev = nullptr,
+                           const double *__restrict__ inv_h = nullptr,
+                           double *__restrict__ moments = nullptr) {
   // XCD-aware block->range remap, same as k_move: MI355X dispatches
   // block b to XCD b%8; giving each XCD one contiguous (spatially
   // compact, since callers keep lists near-Morton-ordered) index range
@@ -438,15 +535,43 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
     Vec3 oo{o.x, o.y, o.z};
     double ot = 0.0;
     int32_t opv = -1;
-    if constexpr (F32)
-      walk_segment32<true>(planes, planes32, nbr, elem[i], o, d, weights[i],
-                           max_steps, add, &oe, &op, &esc, reflective,
-                           face_bc, pidx, pelem, pshift, &od, rt, rp, &oo,
-                           &ot, &opv);
+    // Linear=true: flux plus the four moments (plain atomics; resumed
+    // walks need nothing extra, in_t only seeds t_cur).
+    auto add_lin = [&](int32_t e, double t0, double t1, const WalkState &s) {
+      const double v = (t1 - t0) * s.seg_len * s.weight;
+      double m[4];
+      tet_moments(planes + (int64_t)e * 4, inv_h + (int64_t)e * 4, s, t0, t1,
+                  v, m);
+      if (resp) {
+        for (int k = 0; k < nscores; ++k) {
+          const double r = resp[i * nscores + k];
+          const int64_t at = k * gsz + goff + e;
+          atomicAdd(&flux[at], v * r);
+#pragma unroll
+          for (int f = 0; f < 4; ++f) atomicAdd(&moments[at * 4 + f], m[f] * r);
+        }
+      } else {
+        atomicAdd(&flux[goff + e], v);
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+          atomicAdd(&moments[(goff + e) * 4 + f], m[f]);
+      }
+    };
+    auto walk = [&](auto &tally) {
+      if constexpr (F32)
+        walk_segment32<true>(planes, planes32, nbr, elem[i], o, d, weights[i],
+                             max_steps, tally, &oe, &op, &esc, reflective,
+                             face_bc, pidx, pelem, pshift, &od, rt, rp, &oo,
+                             &ot, &opv);
+      else
+        walk_segment<true>(planes, nbr, elem[i], o, d, weights[i], max_steps,
+                           tally, &oe, &op, &esc, reflective, face_bc, pidx,
+                           pelem, pshift, &od, rt, rp, &oo, &ot, &opv);
+    };
+    if constexpr (Linear)
+      walk(add_lin);
     else
-      walk_segment<true>(planes, nbr, elem[i], o, d, weights[i], max_steps,
-                         add, &oe, &op, &esc, reflective, face_bc, pidx,
-                         pelem, pshift, &od, rt, rp, &oo, &ot, &opv);
+      walk(add);
     int8_t st = 0;
     if (oe == kWalkLost) {
       st = 3;
@@ -493,6 +618,9 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
 // Default is adaptive: 256 slices when the copies fit a 2 GiB HBM
 // budget (trivial against 288 GB for 1M-tet meshes), halved until they
 // do.
+// The linear moments (Engine::moments) are NOT sliced: one device copy,
+// 4x the size of one flux slice, so slicing them too would quadruple the
+// footprint.  Only the flux stays privatized.
 int flux_slices(int64_t flux_doubles) {
   const char *s = getenv("PUMITALLY_FLUX_SLICES");
   int k = s ? atoi(s) : 256;
@@ -542,10 +670,12 @@ int grid_blocks(int64_t work) {
 
 class GpuEngine final : public Engine {
 public:
-  GpuEngine(Mesh mesh, int64_t n, int device, int groups, int scores)
+  GpuEngine(Mesh mesh, int64_t n, int device, int groups, int scores,
+            bool lin)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
+    linear = lin;
     PT_HIP_CHECK(hipSetDevice(device));
     device_ = device;
     s_copy_.create();
@@ -584,6 +714,12 @@ public:
     d_loose_.allocate(1);
     d_lostrec_.allocate((int64_t)kMaxLostRecords * 4);
     PT_HIP_CHECK(hipMemset(d_flux_, 0, fsz_ * slices_ * sizeof(double)));
+    if (linear) {
+      mesh_.build_inv_heights();
+      d_inv_h_ = upload(mesh_.inv_heights);
+      d_moments_.allocate(fsz_ * 4);
+      PT_HIP_CHECK(hipMemset(d_moments_, 0, fsz_ * 4 * sizeof(double)));
+    }
     PT_HIP_CHECK(hipMemset(d_lost_, 0, sizeof(unsigned long long)));
     PT_HIP_CHECK(hipMemset(d_loose_, 0, sizeof(unsigned long long)));
     PT_HIP_CHECK(
@@ -868,6 +1004,15 @@ public:
     k_accumulate_batch<<<grid_blocks(fsz), kBlock, 0, s_comp_>>>(
         d_flux_, d_bsum_, d_bsq_, fsz);
     PT_HIP_CHECK(hipGetLastError());
+    if (linear) {
+      if (!d_msum_) {
+        d_msum_.allocate(fsz * 4);
+        PT_HIP_CHECK(hipMemset(d_msum_, 0, fsz * 4 * sizeof(double)));
+      }
+      k_accumulate_moments<<<grid_blocks(fsz * 4), kBlock, 0, s_comp_>>>(
+          d_moments_, d_msum_, fsz * 4);
+      PT_HIP_CHECK(hipGetLastError());
+    }
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
     nbatches_++;
   }
@@ -899,6 +1044,31 @@ public:
     PT_HIP_CHECK(hipMemcpy(out.data(), d_flux_, fsz * sizeof(double),
                            hipMemcpyDeviceToHost));
     return out;
+  }
+
+  std::vector<double> moments() const override {
+    if (!linear) throw_not_linear();
+    return fetch_moments(d_moments_);
+  }
+  std::vector<double> moment_sum() const override {
+    if (!linear) throw_not_linear();
+    return fetch_moments(d_msum_); // zeros before the first end_batch
+  }
+  std::vector<double> fetch_moments(const double *p) const {
+    std::vector<double> out(fsz_ * 4, 0.0);
+    if (p) {
+      sync();
+      PT_HIP_CHECK(hipMemcpy(out.data(), p, fsz_ * 4 * sizeof(double),
+                             hipMemcpyDeviceToHost));
+    }
+    return out;
+  }
+  void set_moments(const double *m, int64_t n) override {
+    if (!linear) throw_not_linear();
+    if (n != fsz_ * 4) throw std::runtime_error("set_moments size mismatch");
+    sync();
+    PT_HIP_CHECK(hipMemcpy(d_moments_, m, n * sizeof(double),
+                           hipMemcpyHostToDevice));
   }
 
   std::vector<int32_t> elem_ids() const override {
@@ -1182,27 +1352,31 @@ private:
                        const int32_t *in_prev, double *out_o, double *out_t,
                        int32_t *out_prev) {
     const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
-    const auto kernel = walk_fp32 ? k_walk_raw<true> : k_walk_raw<false>;
+    const auto kernel =
+        linear ? (walk_fp32 ? k_walk_raw<true, true> : k_walk_raw<false, true>)
+               : (walk_fp32 ? k_walk_raw<true> : k_walk_raw<false>);
     kernel<<<grid_blocks(n), kBlock, 0, s_comp_>>>(
         d_planes_, d_planes32_, d_nbr_, pos, dest, elem, weights, groups, resp,
         out_pos, out_elem, out_status, out_dest, d_flux_, d_lost_, d_lostrec_,
         n, steps, reflective, d_face_bc_, ngroups, mesh_.nelems, nscores,
-        d_pidx_, d_pelem_, d_pshift_, in_t, in_prev, out_o, out_t, out_prev);
+        d_pidx_, d_pelem_, d_pshift_, in_t, in_prev, out_o, out_t, out_prev,
+        d_inv_h_, d_moments_);
     PT_HIP_CHECK(hipGetLastError());
   }
 
-  template <bool F32, bool Scored, bool Periodic, bool Agg = false>
+  template <bool F32, bool Scored, bool Periodic, bool Agg = false,
+            bool Linear = false>
   void launch_move_one(const double *origin, const double *dest,
                        const int8_t *flying, const double *weights,
                        const uint16_t *groups, const double *resp,
                        int64_t lo, int64_t hi, int steps) {
-    k_move<F32, Scored, Periodic, Agg>
+    k_move<F32, Scored, Periodic, Agg, Linear>
         <<<grid_blocks(hi - lo), kBlock, 0, s_comp_>>>(
         d_planes_, d_planes32_, d_nbr_, grid_view_, d_s2c_, origin, dest,
         flying, weights, groups, ngroups, d_pos_, d_elem_, d_escaped_,
         d_flux_, d_lost_, d_lostrec_, d_loose_, lo, hi, loc_tol_, steps,
         mesh_.nelems, slices_ - 1, reflective, d_face_bc_, resp, nscores,
-        d_pidx_, d_pelem_, d_pshift_);
+        d_pidx_, d_pelem_, d_pshift_, d_inv_h_, d_moments_);
     PT_HIP_CHECK(hipGetLastError());
   }
 
@@ -1212,9 +1386,11 @@ private:
                           int64_t n, int steps) {
     // Chunked launches: a ~2.6M-slot launch keeps each XCD's Morton-
     // contiguous slot range's mesh working set inside its private L2.
-    // Scored / periodic / wave-aggregated moves take dedicated k_move
-    // instantiations; the plain (headline) instantiation compiles without
-    // any of those features.
+    // Scored / periodic / wave-aggregated / linear moves take dedicated
+    // k_move instantiations; the plain (headline) instantiation compiles
+    // without any of those features.  Linear engines take the Linear twin
+    // of whichever instantiation the move would otherwise get (the
+    // wave-aggregated one under the same `agg` condition).
     const int64_t chunk = chunk_particles(n);
     const bool per = d_pidx_ != nullptr;
     // wave aggregation needs a single flat tally key per lane: plain
@@ -1222,22 +1398,27 @@ private:
     const bool agg = wave_agg() && !resp && !groups;
     for (int64_t lo = 0; lo < n; lo += chunk) {
       const int64_t hi = std::min(n, lo + chunk);
-      auto go = [&](auto f32c, auto scoredc, auto perc, auto aggc) {
-        launch_move_one<decltype(f32c)::value, decltype(scoredc)::value,
-                        decltype(perc)::value, decltype(aggc)::value>(
-            origin, dest, flying, weights, groups, resp, lo, hi, steps);
-      };
       using T = std::true_type;
       using F = std::false_type;
-      if (walk_fp32) {
-        if (resp)     per ? go(T{}, T{}, T{}, F{}) : go(T{}, T{}, F{}, F{});
-        else if (agg) per ? go(T{}, F{}, T{}, T{}) : go(T{}, F{}, F{}, T{});
-        else          per ? go(T{}, F{}, T{}, F{}) : go(T{}, F{}, F{}, F{});
-      } else {
-        if (resp)     per ? go(F{}, T{}, T{}, F{}) : go(F{}, T{}, F{}, F{});
-        else if (agg) per ? go(F{}, F{}, T{}, T{}) : go(F{}, F{}, F{}, T{});
-        else          per ? go(F{}, F{}, T{}, F{}) : go(F{}, F{}, F{}, F{});
-      }
+      auto pick = [&](auto linc) {
+        auto go = [&](auto f32c, auto scoredc, auto perc, auto aggc) {
+          launch_move_one<decltype(f32c)::value, decltype(scoredc)::value,
+                          decltype(perc)::value, decltype(aggc)::value,
+                          decltype(linc)::value>(
+              origin, dest, flying, weights, groups, resp, lo, hi, steps);
+        };
+        if (walk_fp32) {
+          if (resp)     per ? go(T{}, T{}, T{}, F{}) : go(T{}, T{}, F{}, F{});
+          else if (agg) per ? go(T{}, F{}, T{}, T{}) : go(T{}, F{}, F{}, T{});
+          else          per ? go(T{}, F{}, T{}, F{}) : go(T{}, F{}, F{}, F{});
+        } else {
+          if (resp)     per ? go(F{}, T{}, T{}, F{}) : go(F{}, T{}, F{}, F{});
+          else if (agg) per ? go(F{}, F{}, T{}, T{}) : go(F{}, F{}, F{}, T{});
+          else          per ? go(F{}, F{}, T{}, F{}) : go(F{}, F{}, F{}, F{});
+        }
+      };
+      if (linear) pick(T{});
+      else        pick(F{});
     }
   }
 
@@ -1331,6 +1512,9 @@ private:
   DeviceBuffer<int8_t> d_flying_[2];
   DeviceBuffer<uint16_t> d_groups_[2];
   DeviceBuffer<double> d_bsum_, d_bsq_;
+  // Linear mode only (null otherwise): 1/heights, the un-sliced moments
+  // [fsz_*4] and their end_batch running sum (allocated on first use).
+  DeviceBuffer<double> d_inv_h_, d_moments_, d_msum_;
   DeviceBuffer<uint32_t> d_face_bc_;
   DeviceBuffer<int32_t> d_pidx_, d_pelem_;
   DeviceBuffer<double> d_pshift_;
@@ -1352,14 +1536,15 @@ private:
 } // namespace
 
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
-                                        int device, int ngroups, int nscores) {
+                                        int device, int ngroups, int nscores,
+                                        bool linear) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= device) {
     (void)hipGetLastError();
     return nullptr;
   }
   return std::make_unique<GpuEngine>(std::move(mesh), num_particles, device,
-                                     ngroups, nscores);
+                                     ngroups, nscores, linear);
 }
 
 } // namespace pumitally

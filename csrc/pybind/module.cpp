@@ -45,20 +45,20 @@ struct PyEngine {
   bool gpu = false;
 
   PyEngine(const Mesh &mesh, int64_t n, const std::string &device,
-           int ngroups = 1, int nscores = 1) {
+           int ngroups = 1, int nscores = 1, bool linear = false) {
     if (device == "cpu") {
-      eng = make_cpu_engine(mesh, n, ngroups, nscores);
+      eng = make_cpu_engine(mesh, n, ngroups, nscores, linear);
     } else {
       int ordinal = 0;
       if (device.rfind("cuda:", 0) == 0) ordinal = std::stoi(device.substr(5));
       else if (device.rfind("gpu:", 0) == 0) ordinal = std::stoi(device.substr(4));
       else if (device != "cuda" && device != "gpu" && device != "auto")
         throw std::runtime_error("device must be cpu/cuda[:N]/auto");
-      eng = make_gpu_engine(mesh, n, ordinal, ngroups, nscores);
+      eng = make_gpu_engine(mesh, n, ordinal, ngroups, nscores, linear);
       if (eng) {
         gpu = true;
       } else if (device == "auto") {
-        eng = make_cpu_engine(mesh, n, ngroups, nscores);
+        eng = make_cpu_engine(mesh, n, ngroups, nscores, linear);
       } else {
         // Fail loudly: a GPU was requested but none is usable.  GPU tests
         // must never fall back silently to the CPU oracle.
@@ -161,16 +161,30 @@ PYBIND11_MODULE(_core, m) {
       .def("write_vtk",
            [](const Mesh &m_, const std::string &path) { write_vtk(path, m_, {}); })
       .def("write_vtk_fields",
-           [](const Mesh &m_, const std::string &path, py::list fields) {
-             std::vector<std::pair<std::string, std::vector<double>>> cd;
-             for (auto item : fields) {
-               auto t = item.cast<py::tuple>();
-               auto name = t[0].cast<std::string>();
-               auto arr = t[1].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
-               cd.emplace_back(name, std::vector<double>(arr.data(), arr.data() + arr.size()));
-             }
-             write_vtk(path, m_, cd);
-           })
+           // fields: [(name, nelems doubles)] cell data; point_fields:
+           // [(name, nverts doubles)] point data (e.g. nodal_flux)
+           [](const Mesh &m_, const std::string &path, py::list fields,
+              py::list point_fields) {
+             auto collect = [](py::list items, int64_t want, const char *what) {
+               std::vector<std::pair<std::string, std::vector<double>>> out;
+               for (auto item : items) {
+                 auto t = item.cast<py::tuple>();
+                 auto name = t[0].cast<std::string>();
+                 auto arr = t[1].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+                 if (want >= 0 && (int64_t)arr.size() != want)
+                   throw std::runtime_error(std::string("write_vtk_fields: ") +
+                                            what + " field '" + name +
+                                            "' has the wrong length");
+                 out.emplace_back(name, std::vector<double>(arr.data(), arr.data() + arr.size()));
+               }
+               return out;
+             };
+             // cell fields keep their historical (unchecked) contract
+             write_vtk(path, m_, collect(fields, -1, "cell"), -1,
+                       collect(point_fields, m_.nverts, "point"));
+           },
+           py::arg("path"), py::arg("fields"),
+           py::arg("point_fields") = py::list())
       .def("write_osh",
            [](const Mesh &m_, const std::string &dir) { write_osh(dir, m_); })
       .def("boundary_faces",
@@ -674,9 +688,13 @@ PYBIND11_MODULE(_core, m) {
         });
 
   py::class_<PyEngine>(m, "Engine")
-      .def(py::init<const Mesh &, int64_t, const std::string &, int, int>(),
+      .def(py::init<const Mesh &, int64_t, const std::string &, int, int,
+                    bool>(),
            py::arg("mesh"), py::arg("num_particles"), py::arg("device") = "auto",
-           py::arg("ngroups") = 1, py::arg("nscores") = 1)
+           py::arg("ngroups") = 1, py::arg("nscores") = 1,
+           py::arg("linear") = false)
+      .def_property_readonly("linear",
+                             [](const PyEngine &e) { return e.eng->linear; })
       .def_property_readonly("ngroups",
                              [](const PyEngine &e) { return e.eng->ngroups; })
       .def_property_readonly("nscores",
@@ -921,6 +939,14 @@ PYBIND11_MODULE(_core, m) {
       .def("set_flux",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> f) {
              e.eng->set_flux(f.data(), (int64_t)f.size());
+           })
+      // linear moment tallies (engine.h); all three throw RuntimeError on
+      // an engine built without linear=True
+      .def("moments", [](const PyEngine &e) { return vec_to_np(e.eng->moments()); })
+      .def("moment_sum", [](const PyEngine &e) { return vec_to_np(e.eng->moment_sum()); })
+      .def("set_moments",
+           [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> m) {
+             e.eng->set_moments(m.data(), (int64_t)m.size());
            })
       .def("set_particle_state",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> pos,

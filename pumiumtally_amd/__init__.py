@@ -66,15 +66,21 @@ class TallyEngine:
 
     device: "auto" (GPU if present, else CPU), "cpu", or "cuda[:N]".
     Semantics follow the reference PumiTally flow; see csrc/core/engine.h.
+
+    linear=True additionally tallies, per (element, local vertex), the first
+    barycentric moments of every track (moments()), from which nodal_flux()
+    and linear_coefficients() give a P1 field; flux() is unchanged by it.
+    Off by default; fixed at construction.
     """
 
     def __init__(self, mesh, num_particles: int, device: str = "auto",
-                 ngroups: int = 1, nscores: int = 1):
+                 ngroups: int = 1, nscores: int = 1, linear: bool = False):
         self._eng = _core.Engine(mesh, num_particles, device, ngroups,
-                                 nscores)
+                                 nscores, bool(linear))
         self.mesh = mesh
         self.ngroups = ngroups
         self.nscores = nscores
+        self.linear = bool(linear)
 
     @property
     def num_particles(self) -> int:
@@ -221,6 +227,73 @@ class TallyEngine:
     def set_flux(self, flux):
         self._eng.set_flux(flux)
 
+    # ---- linear (per-vertex) moment tallies; linear=True engines only ----
+
+    def _tally_shape(self):
+        if self.nscores > 1 and self.ngroups > 1:
+            return (self.nscores, self.ngroups, self.mesh.nelems)
+        if self.nscores > 1:
+            return (self.nscores, self.mesh.nelems)
+        if self.ngroups > 1:
+            return (self.ngroups, self.mesh.nelems)
+        return (self.mesh.nelems,)
+
+    def _require_linear(self, what):
+        if not self.linear:
+            raise RuntimeError(
+                f"{what} needs linear moment tallies: create the engine "
+                "with TallyEngine(..., linear=True)")
+
+    def moments(self):
+        """Raw first barycentric moments of the tallied tracks, shaped
+        flux().shape + (4,): moments()[..., e, f] is the integral of
+        weight * lambda_f along every chord inside element e, lambda_f the
+        barycentric coordinate of the element's local vertex f
+        (mesh.tet2vert[e, f]).  moments().sum(-1) equals flux() up to
+        rounding.  Groups and scores apply exactly as for flux()."""
+        self._require_linear("moments()")
+        return self._eng.moments().reshape(self._tally_shape() + (4,))
+
+    def moment_sum(self):
+        """Moments accumulated over the closed batches (end_batch() adds
+        the per-batch moments here and zeroes them); shaped like moments().
+        Moments carry no sum of squares."""
+        self._require_linear("moment_sum()")
+        return self._eng.moment_sum().reshape(self._tally_shape() + (4,))
+
+    def nodal_flux(self, moments=None):
+        """Lumped-mass nodal (P1) flux, shaped flux().shape[:-1] + (nverts,):
+        phi_v = sum_{e contains v} m[e, local(v)] / sum_{e contains v} vol_e/4.
+        sum_v phi_v * (lumped volume of v) equals the total tallied track
+        length.  moments: optional array shaped like moments() (e.g.
+        moment_sum()) to reconstruct from instead of the current batch."""
+        import numpy as np
+
+        self._require_linear("nodal_flux()")
+        m = self.moments() if moments is None else np.asarray(moments)
+        nv = self.mesh.nverts
+        t2v = np.asarray(self.mesh.tet2vert).reshape(-1)
+        lumped = np.bincount(t2v, weights=np.repeat(
+            np.asarray(self.mesh.volumes) / 4.0, 4), minlength=nv)
+        flat = m.reshape(-1, t2v.size)
+        out = np.stack([np.bincount(t2v, weights=row, minlength=nv)
+                        for row in flat])
+        out = np.divide(out, lumped, out=np.zeros_like(out),
+                        where=lumped > 0)
+        return out.reshape(m.shape[:-2] + (nv,))
+
+    def linear_coefficients(self, moments=None):
+        """Element-local P1 reconstruction, shaped like moments(): the
+        vertex values c_f = (20/vol) * (m_f - sum_g m_g / 5) of the linear
+        function whose moments are m (exact inverse of the tet mass matrix
+        vol/20 * (I + J)).  Their mean over f equals normalized_flux()."""
+        import numpy as np
+
+        self._require_linear("linear_coefficients()")
+        m = self.moments() if moments is None else np.asarray(moments)
+        vol = np.asarray(self.mesh.volumes)[:, None]
+        return (20.0 / vol) * (m - m.sum(axis=-1, keepdims=True) / 5.0)
+
     def elem_ids(self):
         return self._eng.elem_ids()
 
@@ -279,6 +352,8 @@ class TallyEngine:
         import numpy as np
 
         self.synchronize()
+        # linear engines add a "moments" key; everything else is unchanged
+        extra = {"moments": self.moments()} if self.linear else {}
         np.savez_compressed(
             path,
             flux=self.flux(),
@@ -287,6 +362,7 @@ class TallyEngine:
             escaped=self.escaped(),
             num_particles=np.int64(self.num_particles),
             nelems=np.int64(self.mesh.nelems),
+            **extra,
         )
 
     def load_checkpoint(self, path: str):
@@ -297,6 +373,9 @@ class TallyEngine:
            int(d["nelems"]) != self.mesh.nelems:
             raise ValueError("checkpoint does not match engine shape")
         self._eng.set_flux(d["flux"])
+        if self.linear and "moments" in d.files:
+            self._eng.set_moments(
+                np.ascontiguousarray(d["moments"], dtype=np.float64).ravel())
         self._eng.set_particle_state(
             np.ascontiguousarray(d["positions"], dtype=np.float64).ravel(),
             np.ascontiguousarray(d["elem_ids"], dtype=np.int32),
@@ -316,6 +395,14 @@ class TallyEngine:
         return _core.normalize_flux(self.mesh, f)
 
     def write_tally_results(self, filename: str = "fluxresult.vtk"):
+        """Write the normalized tally (legacy .vtk, or .vtu by extension).
+        Linear engines additionally write the point field "nodal_flux"
+        (score 0 summed over groups, like the cell field "flux")."""
+        points = []
+        if self.linear:
+            m0 = self.moments().reshape(self.nscores, self.ngroups,
+                                        self.mesh.nelems, 4)[0].sum(axis=0)
+            points = [("nodal_flux", self.nodal_flux(m0))]
         if self.nscores > 1:
             # one field per score (score 0 keeps the name "flux"),
             # plus per-group fields when also grouped
@@ -330,7 +417,7 @@ class TallyEngine:
                     fields += [(f"{name}_g{g}",
                                 _core.normalize_flux(self.mesh, f[k, g]))
                                for g in range(self.ngroups)]
-            self.mesh.write_vtk_fields(filename, fields)
+            self.mesh.write_vtk_fields(filename, fields, points)
             return
         if self.ngroups > 1:
             # one normalized field per energy group + the total
@@ -338,7 +425,14 @@ class TallyEngine:
             fields = [("flux", _core.normalize_flux(self.mesh, f.sum(axis=0)))]
             fields += [(f"flux_g{g}", _core.normalize_flux(self.mesh, f[g]))
                        for g in range(self.ngroups)]
-            self.mesh.write_vtk_fields(filename, fields)
+            self.mesh.write_vtk_fields(filename, fields, points)
+            return
+        if points:
+            # same two cell fields write_tally_vtk writes
+            self.mesh.write_vtk_fields(
+                filename,
+                [("flux", _core.normalize_flux(self.mesh, self._eng.flux())),
+                 ("volume", self.mesh.volumes)], points)
             return
         _core.write_tally_vtk(filename, self.mesh, self._eng.flux())
 

@@ -151,10 +151,45 @@ void threaded_scored_move() {
           resp.data());
 }
 
+// the same threaded paths (move and walk_raw) in linear mode: per-thread
+// partials must also span the full MOMENTS shape (4x the flux shape)
+void threaded_linear_move() {
+  Mesh m = build_box(6, 6, 6, 1.0, 1.0, 1.0);
+  const int64_t n = 70000;
+  const int G = 2, S = 2;
+  auto e = make_cpu_engine(m, n, G, S, /*linear=*/true);
+  std::mt19937_64 rng(19);
+  std::uniform_real_distribution<double> u(0.02, 0.98);
+  std::vector<double> o(n * 3), d(n * 3), w(n), resp(n * S);
+  std::vector<int8_t> fly(n, 1);
+  std::vector<uint16_t> grp(n);
+  for (int64_t i = 0; i < n * 3; ++i) { o[i] = u(rng); d[i] = u(rng); }
+  for (int64_t i = 0; i < n; ++i) { w[i] = u(rng); grp[i] = rng() % G; }
+  for (int64_t i = 0; i < n * S; ++i) resp[i] = u(rng);
+  e->copy_initial_position(o.data(), n);
+  e->move(o.data(), d.data(), fly.data(), w.data(), n, grp.data(),
+          resp.data());
+  std::vector<int32_t> el = e->elem_ids(), oe(n);
+  std::vector<double> op(n * 3);
+  std::vector<int8_t> st(n);
+  // particles now sit at d in el: walk them back with walk_raw
+  e->walk_raw(n, d.data(), o.data(), el.data(), w.data(), op.data(),
+              oe.data(), st.data(), grp.data(), resp.data());
+  const std::vector<double> f = e->flux(), mo = e->moments();
+  if (mo.size() != f.size() * 4) abort();
+  for (size_t i = 0; i < f.size(); ++i) {
+    const double s4 = mo[4 * i] + mo[4 * i + 1] + mo[4 * i + 2] + mo[4 * i + 3];
+    if (std::fabs(s4 - f[i]) > 1e-9) abort();
+  }
+  e->end_batch();
+  if (e->moment_sum() != mo) abort();
+}
+
 int main() {
   golden();
   fuzz();
   threaded_scored_move();
+  threaded_linear_move();
   // the CPU stateful partitioned engine: step() and step_local() with
   // resampled origins, against the replicated engine
   if (partition_cpu_scenario() != 0) abort();
