@@ -224,6 +224,33 @@ public:
     throw_not_linear();
   }
 
+  // Face-current tallies -- only on engines created with currents=true;
+  // every call below throws otherwise.  For every tallied crossing where the
+  // walk leaves element e through local face f (the face opposite local
+  // vertex f; flat face index e*4+f as in the boundary-face tables) the
+  // particle's weight is added to J[e, f]: the outward partial current J+
+  // integrated over the face.  No track length and no cosine enter.  Groups
+  // and scores apply exactly as for flux (group offset, weight *
+  // responses[i,k] per score; null responses: score 0 only).  Layout:
+  // [nscores x ngroups x nelems x 4], local face fastest, index = (flux
+  // index)*4 + f.  A crossing is every exit-face selection of walk_advance
+  // with t_exit < 1 on a tallied walk (neighbor step, vacuum clip, handoff,
+  // reflective or periodic restart, zero-length slivers included); the
+  // final partial segment, untallied walks and phase-A relocation count
+  // nothing.  The flux tally itself is produced exactly as without the
+  // option.  end_batch() adds the per-batch currents into current_sum and
+  // their squares into current_sum_sq (a per-entry variance is meaningful
+  // here, unlike for the moments) and zeroes them.
+  virtual std::vector<double> currents() const { throw_not_currents(); }
+  virtual std::vector<double> current_sum() const { throw_not_currents(); }
+  virtual std::vector<double> current_sum_sq() const { throw_not_currents(); }
+  // Overwrite the per-batch currents (checkpoint restore); n must be the
+  // full currents size.
+  virtual void set_currents(const double *j, int64_t n) {
+    (void)j; (void)n;
+    throw_not_currents();
+  }
+
   // Restore particle state (checkpoint/resume support -- the reference has
   // none; a crash there loses the whole batch).
   virtual void set_particle_state(const double *pos, const int32_t *elem,
@@ -259,6 +286,12 @@ public:
   // (make_*_engine's trailing argument); read-only afterwards.
   bool linear = false;
 
+  // Face-current tallies enabled (see currents()).  Fixed at construction
+  // (make_*_engine's trailing argument); read-only afterwards.  Cannot be
+  // combined with linear.  (Named face_currents because currents() is the
+  // accessor.)
+  bool face_currents = false;
+
   // fp32-traversal fast path (walk.h walk_advance32): candidate exit-face
   // decisions in fp32, crossings/tallies in fp64.  Controlled by
   // PUMITALLY_WALK=fp32|fp64; both engines honor it so CPU remains the
@@ -281,6 +314,10 @@ protected:
   [[noreturn]] static void throw_not_linear() {
     throw std::runtime_error(
         "linear moment tallies are off: create the engine with linear=true");
+  }
+  [[noreturn]] static void throw_not_currents() {
+    throw std::runtime_error(
+        "face-current tallies are off: create the engine with currents=true");
   }
 };
 
@@ -325,12 +362,21 @@ inline double loc_tol_rel() {
 
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
                                         int ngroups = 1, int nscores = 1,
-                                        bool linear = false);
+                                        bool linear = false,
+                                        bool currents = false);
 
 // Returns nullptr when no HIP device is available.
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
                                         int device, int ngroups = 1,
-                                        int nscores = 1, bool linear = false);
+                                        int nscores = 1, bool linear = false,
+                                        bool currents = false);
+
+// make_*_engine reject the one unsupported option pair up front.
+inline void check_tally_options(bool linear, bool currents) {
+  if (linear && currents)
+    throw std::invalid_argument(
+        "currents=true cannot be combined with linear=true (not implemented)");
+}
 
 // Normalized flux = flux / element volume (volume-only, matching the
 // reference implementation rather than its docstring:

@@ -30,16 +30,18 @@ namespace {
 
 class CpuEngine final : public Engine {
 public:
-  CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin)
+  CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin, bool cur)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
     linear = lin;
+    face_currents = cur;
     flux_.assign(mesh_.nelems * ngroups * nscores, 0.0);
     if (linear) {
       mesh_.build_inv_heights();
       moments_.assign(flux_.size() * 4, 0.0);
     }
+    if (face_currents) currents_.assign(flux_.size() * 4, 0.0);
     pos_.resize(n_ * 3);
     elem_.assign(n_, 0);
     escaped_.assign(n_, 0);
@@ -117,6 +119,10 @@ public:
       // shape (4x the flux shape; empty otherwise, never written then)
       std::vector<std::vector<double>> partial_m(
           nthreads, std::vector<double>(moments_.size(), 0.0));
+      // ... and, with face currents on, a partial of the full currents
+      // shape (scores included, like the flux partial above)
+      std::vector<std::vector<double>> partial_c(
+          nthreads, std::vector<double>(currents_.size(), 0.0));
       std::atomic<int64_t> lost{0}, reloc{0};
       std::vector<std::thread> workers;
       const int64_t per = (n + nthreads - 1) / nthreads;
@@ -126,8 +132,8 @@ public:
           int64_t my_lost = 0, my_reloc = 0;
           for (int64_t i = lo; i < hi; ++i)
             move_one(origin, dest, flying, weights, groups, responses, i,
-                     steps, partial[t].data(), partial_m[t].data(), my_lost,
-                     my_reloc);
+                     steps, partial[t].data(), partial_m[t].data(),
+                     partial_c[t].data(), my_lost, my_reloc);
           lost += my_lost;
           reloc += my_reloc;
         });
@@ -139,6 +145,9 @@ public:
       for (int t = 0; t < nthreads; ++t)
         for (size_t e = 0; e < moments_.size(); ++e)
           moments_[e] += partial_m[t][e];
+      for (int t = 0; t < nthreads; ++t)
+        for (size_t e = 0; e < currents_.size(); ++e)
+          currents_[e] += partial_c[t][e];
       stats_.lost_particles += lost.load();
       stats_.relocated += reloc.load();
       stats_.moves++;
@@ -147,7 +156,7 @@ public:
     int64_t lost = 0, reloc = 0;
     for (int64_t i = 0; i < n; ++i)
       move_one(origin, dest, flying, weights, groups, responses, i, steps,
-               flux_.data(), moments_.data(), lost, reloc);
+               flux_.data(), moments_.data(), currents_.data(), lost, reloc);
     stats_.lost_particles += lost;
     stats_.relocated += reloc;
     stats_.moves++;
@@ -158,8 +167,8 @@ public:
   void move_one(const double *origin, const double *dest,
                 const int8_t *flying, const double *weights,
                 const uint16_t *groups, const double *responses, int64_t i,
-                int steps, double *flux_out, double *mom_out, int64_t &lost,
-                int64_t &reloc) {
+                int steps, double *flux_out, double *mom_out, double *cur_out,
+                int64_t &lost, int64_t &reloc) {
     if (!flying[i]) return;
     Vec3 o{pos_[i * 3], pos_[i * 3 + 1], pos_[i * 3 + 2]};
     if (origin && !escaped_[i]) {
@@ -218,6 +227,17 @@ public:
         add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
       };
       walk(add_lin);
+    } else if (face_currents) {
+      // an escaped particle leaving again where it sits is one departure
+      // (walk.h walk_current_face)
+      bool reexit = escaped_[i] != 0;
+      auto add_cur = [&](int32_t e, double t0, double t1, const WalkState &s,
+                         int exit_face) {
+        const int face = walk_current_face<true>(
+            reexit, mesh_.nbr.data(), e, exit_face, t1, reflective, bc, pix);
+        add_current(flux_out, cur_out, goff, gsz, resp, e, t0, t1, s, face);
+      };
+      walk(add_cur);
     } else {
       walk(add);
     }
@@ -251,6 +271,8 @@ public:
           nthreads, std::vector<double>(flux_.size(), 0.0));
       std::vector<std::vector<double>> partial_m(
           nthreads, std::vector<double>(moments_.size(), 0.0));
+      std::vector<std::vector<double>> partial_c(
+          nthreads, std::vector<double>(currents_.size(), 0.0));
       std::atomic<int64_t> lost{0};
       std::vector<std::thread> workers;
       const int64_t per = (n + nthreads - 1) / nthreads;
@@ -262,7 +284,8 @@ public:
             walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
                          out_elem, out_status, out_dest, in_t, in_prev,
                          out_o, out_t, out_prev, i, steps,
-                         partial[t].data(), partial_m[t].data(), my_lost);
+                         partial[t].data(), partial_m[t].data(),
+                         partial_c[t].data(), my_lost);
           lost += my_lost;
         });
       }
@@ -272,6 +295,9 @@ public:
       for (int t = 0; t < nthreads; ++t)
         for (size_t e = 0; e < moments_.size(); ++e)
           moments_[e] += partial_m[t][e];
+      for (int t = 0; t < nthreads; ++t)
+        for (size_t e = 0; e < currents_.size(); ++e)
+          currents_[e] += partial_c[t][e];
       stats_.lost_particles += lost.load();
       return;
     }
@@ -280,7 +306,7 @@ public:
       walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
                    out_elem, out_status, out_dest, in_t, in_prev, out_o,
                    out_t, out_prev, i, steps, flux_.data(), moments_.data(),
-                   lost);
+                   currents_.data(), lost);
     stats_.lost_particles += lost;
   }
 
@@ -291,7 +317,8 @@ public:
                     double *out_dest, const double *in_t,
                     const int32_t *in_prev, double *out_o, double *out_t,
                     int32_t *out_prev, int64_t i, int steps,
-                    double *flux_out, double *mom_out, int64_t &lost) {
+                    double *flux_out, double *mom_out, double *cur_out,
+                    int64_t &lost) {
     {
       const Vec3 o{pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]};
       const Vec3 d{dest[i * 3], dest[i * 3 + 1], dest[i * 3 + 2]};
@@ -345,6 +372,15 @@ public:
           add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
         };
         walk(add_lin);
+      } else if (face_currents) {
+        // A resumed walk starts inside its element, so the crossing its
+        // sender counted is not counted again.
+        auto add_cur = [&](int32_t e, double t0, double t1,
+                           const WalkState &s, int exit_face) {
+          add_current(flux_out, cur_out, goff, gsz, resp, e, t0, t1, s,
+                      exit_face);
+        };
+        walk(add_cur);
       } else {
         walk(add);
       }
@@ -396,6 +432,17 @@ public:
         moments_[e] = 0.0;
       }
     }
+    if (face_currents) {
+      if (current_sum_.empty()) {
+        current_sum_.assign(currents_.size(), 0.0);
+        current_sq_.assign(currents_.size(), 0.0);
+      }
+      for (size_t e = 0; e < currents_.size(); ++e) {
+        current_sum_[e] += currents_[e];
+        current_sq_[e] += currents_[e] * currents_[e];
+        currents_[e] = 0.0;
+      }
+    }
     nbatches_++;
   }
   std::vector<double> batch_sum() const override {
@@ -442,6 +489,27 @@ public:
     std::memcpy(moments_.data(), m, n * sizeof(double));
   }
 
+  std::vector<double> currents() const override {
+    if (!face_currents) throw_not_currents();
+    return currents_;
+  }
+  std::vector<double> current_sum() const override {
+    if (!face_currents) throw_not_currents();
+    return current_sum_.empty() ? std::vector<double>(currents_.size(), 0.0)
+                                : current_sum_;
+  }
+  std::vector<double> current_sum_sq() const override {
+    if (!face_currents) throw_not_currents();
+    return current_sq_.empty() ? std::vector<double>(currents_.size(), 0.0)
+                               : current_sq_;
+  }
+  void set_currents(const double *j, int64_t n) override {
+    if (!face_currents) throw_not_currents();
+    if (n != (int64_t)currents_.size())
+      throw std::runtime_error("set_currents size mismatch");
+    std::memcpy(currents_.data(), j, n * sizeof(double));
+  }
+
   void set_particle_state(const double *pos, const int32_t *elem,
                           const uint8_t *escaped, int64_t n) override {
     check_n(n);
@@ -478,6 +546,26 @@ private:
     }
   }
 
+  // Face-current contribution (face walk callback): the flux add is the
+  // plain path's expression and order, so flux stays bit-identical to an
+  // engine without the option; a crossing (exit_face >= 0) adds the weight
+  // at (flux index)*4 + exit_face.
+  void add_current(double *flux_out, double *cur_out, int64_t goff,
+                   int64_t gsz, const double *resp, int32_t e, double t0,
+                   double t1, const WalkState &s, int exit_face) const {
+    const double v = (t1 - t0) * s.seg_len * s.weight;
+    if (!resp) {
+      flux_out[goff + e] += v;
+      if (exit_face >= 0) cur_out[(goff + e) * 4 + exit_face] += s.weight;
+      return;
+    }
+    for (int k = 0; k < nscores; ++k) {
+      flux_out[k * gsz + goff + e] += v * resp[k];
+      if (exit_face >= 0)
+        cur_out[(k * gsz + goff + e) * 4 + exit_face] += s.weight * resp[k];
+    }
+  }
+
   void record_lost(int64_t i, Vec3 p) {
     const int64_t k = lost_rec_n_.fetch_add(1);
     if (k < kMaxLostRecords) {
@@ -493,6 +581,8 @@ private:
   double loc_tol_;
   std::vector<double> flux_, pos_, batch_sum_, batch_sq_;
   std::vector<double> moments_, moment_sum_; // linear mode only, else empty
+  // face currents only, else empty
+  std::vector<double> currents_, current_sum_, current_sq_;
   int64_t nbatches_ = 0;
   std::vector<int32_t> elem_;
   std::vector<uint8_t> escaped_;
@@ -507,9 +597,10 @@ private:
 
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
                                         int ngroups, int nscores,
-                                        bool linear) {
+                                        bool linear, bool currents) {
+  check_tally_options(linear, currents);
   return std::make_unique<CpuEngine>(std::move(mesh), num_particles, ngroups,
-                                     nscores, linear);
+                                     nscores, linear, currents);
 }
 
 } // namespace pumitally

@@ -9,7 +9,9 @@
 
 namespace pumitally {
 
-std::unique_ptr<Engine> make_gpu_engine(Mesh, int64_t, int, int, int, bool) {
+std::unique_ptr<Engine> make_gpu_engine(Mesh, int64_t, int, int, int, bool linear,
+                                        bool currents) {
+  check_tally_options(linear, currents);
   return nullptr;
 }
 

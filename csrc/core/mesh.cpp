@@ -98,6 +98,48 @@ void Mesh::build_inv_heights() {
     inv_heights[i] = 1.0 / plane_eval(planes[i], vert(tet2vert[i]));
 }
 
+std::vector<int64_t> Mesh::face_twins() const {
+  if (nbr.size() != (size_t)nelems * 4)
+    throw std::runtime_error("face_twins: call finalize() first");
+  std::vector<int64_t> twins((size_t)nelems * 4, -1);
+  for (int64_t e = 0; e < nelems; ++e)
+    for (int f = 0; f < 4; ++f) {
+      const int64_t fidx = e * 4 + f;
+      const int32_t nb = nbr[fidx];
+      if (nb >= 0) {
+        for (int g = 0; g < 4; ++g)
+          if (nbr[(int64_t)nb * 4 + g] == e) twins[fidx] = (int64_t)nb * 4 + g;
+      } else if (nb == -1 && !periodic_idx.empty() && periodic_idx[fidx] >= 0) {
+        // the paired face: the face of the entry element whose own pair
+        // leads back here with the opposite translation
+        const int32_t pk = periodic_idx[fidx];
+        const int32_t pe = periodic_elem[pk];
+        for (int g = 0; g < 4; ++g) {
+          const int32_t q = periodic_idx[(int64_t)pe * 4 + g];
+          if (q < 0 || periodic_elem[q] != e) continue;
+          bool opposite = true;
+          for (int k = 0; k < 3; ++k)
+            opposite &= periodic_shift[(size_t)q * 3 + k] ==
+                        -periodic_shift[(size_t)pk * 3 + k];
+          if (opposite) twins[fidx] = (int64_t)pe * 4 + g;
+        }
+      }
+    }
+  return twins;
+}
+
+std::vector<double> Mesh::face_areas() const {
+  std::vector<double> areas((size_t)nelems * 4);
+  for (int64_t e = 0; e < nelems; ++e)
+    for (int f = 0; f < 4; ++f) {
+      const Vec3 a = vert(tet2vert[e * 4 + kFaceVerts[f][0]]);
+      const Vec3 b = vert(tet2vert[e * 4 + kFaceVerts[f][1]]);
+      const Vec3 c = vert(tet2vert[e * 4 + kFaceVerts[f][2]]);
+      areas[e * 4 + f] = 0.5 * norm(cross(b - a, c - a));
+    }
+  return areas;
+}
+
 bool Mesh::contains(int32_t t, Vec3 p, double tol) const {
   for (int f = 0; f < 4; ++f)
     if (plane_eval(planes[t * 4 + f], p) < -tol) return false;

@@ -96,6 +96,13 @@ struct Mesh {
   std::vector<double> inv_heights;
   void build_inv_heights();
 
+  // nelems*4: flat index (elem*4+f) of the same face seen from the
+  // neighbor; for a periodic face the paired face; -1 for every other
+  // boundary face and for a partition-cut face (nbr < -1).
+  std::vector<int64_t> face_twins() const;
+  // nelems*4: area of local face f, from the coordinates.
+  std::vector<double> face_areas() const;
+
   // Build adjacency, planes, volumes, bbox and the localization grid.
   // Reorients negatively-oriented tets in place (swaps verts 2,3).
   void finalize();

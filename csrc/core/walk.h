@@ -106,20 +106,69 @@ PT_HD void periodic_restart(WalkState &s, double t_clamped,
 // neighbor / a boundary clip / a handoff / a reflective or periodic
 // restart).  The crossing covers the segment parameter range
 // [s.t_cur, t1] of the walk state's CURRENT (o, d, seg_len, weight); it is
-// always called before a restart rebases them.  Two callback forms:
+// always called before a restart rebases them.  exit_face is the local face
+// the walk leaves s.elem through at t1, or -1 at the final-segment site
+// (the destination lies inside the element).  Three callback forms:
 //   legacy  void(int32_t elem, double length_times_weight)
 //   rich    void(int32_t elem, double t0, double t1, const WalkState &)
+//   face    void(int32_t elem, double t0, double t1, const WalkState &,
+//                int exit_face)
 // The rich form additionally sees the entry/exit parameters and the walk
 // state (the linear moment tallies need the chord's end points, see
-// tet_moments).  The legacy form receives exactly the expression it always
-// did, so plain flux tallies are bit-for-bit unchanged.
+// tet_moments); the face form also sees the exit face (the face-current
+// tallies count the crossing there).  The legacy and rich forms receive
+// exactly what they always did, so plain flux tallies are bit-for-bit
+// unchanged.
 template <class FluxAdd>
-PT_HD void walk_contribute(FluxAdd &add, const WalkState &s, double t1) {
+PT_HD void walk_contribute(FluxAdd &add, const WalkState &s, double t1,
+                           int exit_face) {
   if constexpr (std::is_invocable_v<FluxAdd &, int32_t, double, double,
-                                    const WalkState &>)
+                                    const WalkState &, int>)
+    add(s.elem, s.t_cur, t1, s, exit_face);
+  else if constexpr (std::is_invocable_v<FluxAdd &, int32_t, double, double,
+                                         const WalkState &>)
     add(s.elem, s.t_cur, t1, s);
   else
     add(s.elem, (t1 - s.t_cur) * s.seg_len * s.weight);
+}
+
+// True when a walk leaving `elem` through local face `face` is clipped there
+// as escaped: a boundary face that is neither periodic nor reflective --
+// the tests walk_advance applies, in its order.
+template <bool Periodic = false>
+PT_HD bool walk_exit_is_vacuum(const int32_t *__restrict__ nbr, int32_t elem,
+                               int face, bool reflective,
+                               const uint32_t *__restrict__ face_bc,
+                               const int32_t *__restrict__ pidx) {
+  const int64_t fidx = (int64_t)elem * 4 + face;
+  if (nbr[fidx] != -1) return false;
+  if constexpr (Periodic) {
+    if (pidx && pidx[fidx] >= 0) return false;
+  }
+  return !(reflective ||
+           (face_bc && ((face_bc[fidx >> 5] >> (fidx & 31)) & 1u)));
+}
+
+// Face-current rule for a particle that move() finds already flagged
+// escaped: it still sits on the vacuum face it left through (phase A does
+// not relocate it), and a walk that leaves again right there -- first
+// contribution, a vacuum clip within the walk's t tolerance of its start --
+// is the SAME departure, not a second one.  Returns the face to book the
+// crossing on (-1: none) and clears `pending` after the first contribution.
+template <bool Periodic = false>
+PT_HD int walk_current_face(bool &pending, const int32_t *__restrict__ nbr,
+                            int32_t elem, int exit_face, double t1,
+                            bool reflective,
+                            const uint32_t *__restrict__ face_bc,
+                            const int32_t *__restrict__ pidx) {
+  if (pending) {
+    pending = false;
+    if (exit_face >= 0 && t1 <= kWalkTEps &&
+        walk_exit_is_vacuum<Periodic>(nbr, elem, exit_face, reflective,
+                                      face_bc, pidx))
+      return -1;
+  }
+  return exit_face;
 }
 
 // First barycentric moments of one crossing: m[f] = integral over the chord
@@ -210,7 +259,7 @@ PT_HD bool walk_advance(const Plane *__restrict__ planes,
   if (exit_face < 0 || t_exit >= 1.0) {
     // Destination lies inside this element: tally the final partial
     // segment and stop (reference: reached_destination, last_exit==-1).
-    if (s.tally) walk_contribute(add, s, 1.0);
+    if (s.tally) walk_contribute(add, s, 1.0, -1);
     *out_elem = s.elem;
     *out_pos = s.d;
     *out_escaped = false;
@@ -218,7 +267,7 @@ PT_HD bool walk_advance(const Plane *__restrict__ planes,
   }
 
   const double t_clamped = t_exit > s.t_cur ? t_exit : s.t_cur;
-  if (s.tally) walk_contribute(add, s, t_clamped);
+  if (s.tally) walk_contribute(add, s, t_clamped, exit_face);
 
   const int32_t next = nbr[(int64_t)s.elem * 4 + exit_face];
   if (next == -1) {
@@ -335,7 +384,7 @@ PT_HD bool walk_advance32(const Plane *__restrict__ planes,
   }
 
   if (exit_face < 0 || t_exit >= 1.0f) {
-    if (s.tally) walk_contribute(add, s, 1.0);
+    if (s.tally) walk_contribute(add, s, 1.0, -1);
     *out_elem = s.elem;
     *out_pos = s.d;
     *out_escaped = false;
@@ -349,7 +398,7 @@ PT_HD bool walk_advance32(const Plane *__restrict__ planes,
   double t64 = (vo64 - vd64) > 0.0 ? vo64 / (vo64 - vd64) : s.t_cur;
   if (t64 > 1.0) t64 = 1.0;
   const double t_clamped = t64 > s.t_cur ? t64 : s.t_cur;
-  if (s.tally) walk_contribute(add, s, t_clamped);
+  if (s.tally) walk_contribute(add, s, t_clamped, exit_face);
 
   const int32_t next = nbr[(int64_t)s.elem * 4 + exit_face];
   if (next == -1) {

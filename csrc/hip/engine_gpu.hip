@@ -304,6 +304,16 @@ wave_agg_atomic_add_linear(double *__restrict__ flux,
   }
 }
 
+// Face currents under the aggregated dispatch: plain atomics (default) or
+// the same run aggregation keyed on the flat face index el*4+f
+// (PUMITALLY_CURRENTS_AGG=1).  Read per engine, at construction, so one
+// process can compare the two (benchmarks/currents_cost.py; figures in
+// profiles/README.md).
+inline bool currents_keyed_agg() {
+  const char *s = getenv("PUMITALLY_CURRENTS_AGG");
+  return s ? atoi(s) != 0 : false;
+}
+
 inline bool wave_agg() {
   static bool v = [] {
     const char *s = getenv("PUMITALLY_WAVE_AGG");
@@ -327,8 +337,16 @@ inline bool wave_agg() {
 // (walk.h tet_moments) into `moments` -- ONE un-sliced array, see
 // flux_slices -- reading `inv_h`.  Linear=false instantiations never read
 // either trailing argument.
+//
+// Currents=true (never together with Linear) additionally adds the weight
+// of every crossing to `cur` at (flux index)*4 + exit face -- ONE un-sliced
+// array like the moments.  Under Agg the flux still goes through
+// wave_agg_atomic_add first thing in the callback, i.e. with the active set
+// the non-currents kernel has there; the current is one plain atomicAdd per
+// crossing, or with cur_keyed the same run aggregation keyed on el*4+f.
+// Currents=false instantiations never read cur / cur_keyed.
 template <bool F32, bool Scored = false, bool Periodic = false,
-          bool Agg = false, bool Linear = false>
+          bool Agg = false, bool Linear = false, bool Currents = false>
 __global__ void k_move(const Plane *__restrict__ planes,
                        const Plane32 *__restrict__ planes32,
                        const int32_t *__restrict__ nbr, GridView grid,
@@ -353,7 +371,10 @@ __global__ void k_move(const Plane *__restrict__ planes,
                        const int32_t *__restrict__ pelem = nullptr,
                        const double *__restrict__ pshift = nullptr,
                        const double *__restrict__ inv_h = nullptr,
-                       double *__restrict__ moments = nullptr) {
+                       double *__restrict__ moments = nullptr,
+                       double *__restrict__ cur = nullptr,
+                       bool cur_keyed = false) {
+  static_assert(!(Linear && Currents), "linear + currents is not built");
   // Scored=false, Periodic=false is the headline instantiation:
   // resp/nscores/pidx are unused, the slice stride stays nelems*ngroups,
   // and the walk compiles without the score loop or the periodic branch --
@@ -440,6 +461,47 @@ __global__ void k_move(const Plane *__restrict__ planes,
       for (int f = 0; f < 4; ++f)
         atomicAdd(&moments[(goff + el) * 4 + f], m[f]);
     };
+    // Face-current contribution (face walk callback): the plain path's flux
+    // value and atomics, then the crossing's weight at (flux index)*4 +
+    // exit_face.  exit_face_in is -1 at the final-segment site, where the
+    // current code folds away after inlining.  An escaped particle leaving
+    // again where it sits is one departure (walk.h walk_current_face); the
+    // flag is read only by Currents instantiations.
+    bool reexit = false;
+    if constexpr (Currents) reexit = escaped[i] != 0;
+    auto add_cur = [&](int32_t el, double t0, double t1, const WalkState &s,
+                       int exit_face_in) {
+      const int exit_face = walk_current_face<Periodic>(
+          reexit, nbr, el, exit_face_in, t1, reflective, face_bc, pidx);
+      const double v = (t1 - t0) * s.seg_len * s.weight;
+      if constexpr (Scored) {
+        const int64_t gsz = (int64_t)ngroups * nelems;
+        if (resp) {
+          for (int k = 0; k < nscores; ++k) {
+            const double r = resp[c * nscores + k];
+            const int64_t at = k * gsz + goff + el;
+            atomicAdd(&flux[at], v * r);
+            if (exit_face >= 0)
+              atomicAdd(&cur[at * 4 + exit_face], s.weight * r);
+          }
+          return;
+        }
+      } else if constexpr (Agg) {
+        wave_agg_atomic_add(flux, el, v);
+        if (exit_face >= 0) {
+          // keyed form: int32 key; the engine enables it only while
+          // nelems*4 fits
+          if (cur_keyed)
+            wave_agg_atomic_add(cur, el * 4 + exit_face, s.weight);
+          else
+            atomicAdd(&cur[(int64_t)el * 4 + exit_face], s.weight);
+        }
+        return;
+      }
+      atomicAdd(&flux[goff + el], v);
+      if (exit_face >= 0)
+        atomicAdd(&cur[(goff + el) * 4 + exit_face], s.weight);
+    };
     auto walk = [&](auto &tally) {
       if constexpr (F32)
         walk_segment32<Periodic>(planes, planes32, nbr, e, o, d, weights[c],
@@ -453,6 +515,8 @@ __global__ void k_move(const Plane *__restrict__ planes,
     };
     if constexpr (Linear)
       walk(add_lin);
+    else if constexpr (Currents)
+      walk(add_cur);
     else
       walk(add);
     if (out_elem == kWalkLost) {
@@ -473,7 +537,7 @@ __global__ void k_move(const Plane *__restrict__ planes,
   }
 }
 
-template <bool F32, bool Linear = false>
+template <bool F32, bool Linear = false, bool Currents = false>
 __global__ void k_walk_raw(const Plane *__restrict__ planes,
                            const Plane32 *__restrict__ planes32,
                            const int32_t *__restrict__ nbr,
@@ -502,7 +566,9 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
                            double *__restrict__ out_t = nullptr,
                            int32_t *__restrict__ out_prev = nullptr,
                            const double *__restrict__ inv_h = nullptr,
-                           double *__restrict__ moments = nullptr) {
+                           double *__restrict__ moments = nullptr,
+                           double *__restrict__ cur = nullptr) {
+  static_assert(!(Linear && Currents), "linear + currents is not built");
   // XCD-aware block->range remap, same as k_move: MI355X dispatches
   // block b to XCD b%8; giving each XCD one contiguous (spatially
   // compact, since callers keep lists near-Morton-ordered) index range
@@ -557,6 +623,25 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
           atomicAdd(&moments[(goff + e) * 4 + f], m[f]);
       }
     };
+    // Currents=true: flux plus the crossing's weight on its exit face
+    // (plain atomics).  A resumed walk starts inside its element, so the
+    // crossing its sender counted is not counted again.
+    auto add_cur = [&](int32_t e, double t0, double t1, const WalkState &s,
+                       int exit_face) {
+      const double v = (t1 - t0) * s.seg_len * s.weight;
+      if (resp) {
+        for (int k = 0; k < nscores; ++k) {
+          const double r = resp[i * nscores + k];
+          const int64_t at = k * gsz + goff + e;
+          atomicAdd(&flux[at], v * r);
+          if (exit_face >= 0) atomicAdd(&cur[at * 4 + exit_face], s.weight * r);
+        }
+      } else {
+        atomicAdd(&flux[goff + e], v);
+        if (exit_face >= 0)
+          atomicAdd(&cur[(goff + e) * 4 + exit_face], s.weight);
+      }
+    };
     auto walk = [&](auto &tally) {
       if constexpr (F32)
         walk_segment32<true>(planes, planes32, nbr, elem[i], o, d, weights[i],
@@ -570,6 +655,8 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
     };
     if constexpr (Linear)
       walk(add_lin);
+    else if constexpr (Currents)
+      walk(add_cur);
     else
       walk(add);
     int8_t st = 0;
@@ -671,11 +758,12 @@ int grid_blocks(int64_t work) {
 class GpuEngine final : public Engine {
 public:
   GpuEngine(Mesh mesh, int64_t n, int device, int groups, int scores,
-            bool lin)
+            bool lin, bool cur)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
     linear = lin;
+    face_currents = cur;
     PT_HIP_CHECK(hipSetDevice(device));
     device_ = device;
     s_copy_.create();
@@ -719,6 +807,12 @@ public:
       d_inv_h_ = upload(mesh_.inv_heights);
       d_moments_.allocate(fsz_ * 4);
       PT_HIP_CHECK(hipMemset(d_moments_, 0, fsz_ * 4 * sizeof(double)));
+    }
+    if (face_currents) {
+      d_cur_.allocate(fsz_ * 4);
+      PT_HIP_CHECK(hipMemset(d_cur_, 0, fsz_ * 4 * sizeof(double)));
+      // the keyed aggregation carries el*4+f in an int32 lane value
+      cur_keyed_ = currents_keyed_agg() && mesh_.nelems < ((int64_t)1 << 29);
     }
     PT_HIP_CHECK(hipMemset(d_lost_, 0, sizeof(unsigned long long)));
     PT_HIP_CHECK(hipMemset(d_loose_, 0, sizeof(unsigned long long)));
@@ -1013,6 +1107,17 @@ public:
           d_moments_, d_msum_, fsz * 4);
       PT_HIP_CHECK(hipGetLastError());
     }
+    if (face_currents) {
+      if (!d_csum_) {
+        d_csum_.allocate(fsz * 4);
+        d_csq_.allocate(fsz * 4);
+        PT_HIP_CHECK(hipMemset(d_csum_, 0, fsz * 4 * sizeof(double)));
+        PT_HIP_CHECK(hipMemset(d_csq_, 0, fsz * 4 * sizeof(double)));
+      }
+      k_accumulate_batch<<<grid_blocks(fsz * 4), kBlock, 0, s_comp_>>>(
+          d_cur_, d_csum_, d_csq_, fsz * 4);
+      PT_HIP_CHECK(hipGetLastError());
+    }
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
     nbatches_++;
   }
@@ -1068,6 +1173,27 @@ public:
     if (n != fsz_ * 4) throw std::runtime_error("set_moments size mismatch");
     sync();
     PT_HIP_CHECK(hipMemcpy(d_moments_, m, n * sizeof(double),
+                           hipMemcpyHostToDevice));
+  }
+
+  // Face currents share the moments' shape and readback.
+  std::vector<double> currents() const override {
+    if (!face_currents) throw_not_currents();
+    return fetch_moments(d_cur_);
+  }
+  std::vector<double> current_sum() const override {
+    if (!face_currents) throw_not_currents();
+    return fetch_moments(d_csum_); // zeros before the first end_batch
+  }
+  std::vector<double> current_sum_sq() const override {
+    if (!face_currents) throw_not_currents();
+    return fetch_moments(d_csq_);
+  }
+  void set_currents(const double *j, int64_t n) override {
+    if (!face_currents) throw_not_currents();
+    if (n != fsz_ * 4) throw std::runtime_error("set_currents size mismatch");
+    sync();
+    PT_HIP_CHECK(hipMemcpy(d_cur_, j, n * sizeof(double),
                            hipMemcpyHostToDevice));
   }
 
@@ -1354,29 +1480,33 @@ private:
     const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
     const auto kernel =
         linear ? (walk_fp32 ? k_walk_raw<true, true> : k_walk_raw<false, true>)
-               : (walk_fp32 ? k_walk_raw<true> : k_walk_raw<false>);
+        : face_currents
+            ? (walk_fp32 ? k_walk_raw<true, false, true>
+                         : k_walk_raw<false, false, true>)
+            : (walk_fp32 ? k_walk_raw<true> : k_walk_raw<false>);
     kernel<<<grid_blocks(n), kBlock, 0, s_comp_>>>(
         d_planes_, d_planes32_, d_nbr_, pos, dest, elem, weights, groups, resp,
         out_pos, out_elem, out_status, out_dest, d_flux_, d_lost_, d_lostrec_,
         n, steps, reflective, d_face_bc_, ngroups, mesh_.nelems, nscores,
         d_pidx_, d_pelem_, d_pshift_, in_t, in_prev, out_o, out_t, out_prev,
-        d_inv_h_, d_moments_);
+        d_inv_h_, d_moments_, d_cur_);
     PT_HIP_CHECK(hipGetLastError());
   }
 
   template <bool F32, bool Scored, bool Periodic, bool Agg = false,
-            bool Linear = false>
+            bool Linear = false, bool Currents = false>
   void launch_move_one(const double *origin, const double *dest,
                        const int8_t *flying, const double *weights,
                        const uint16_t *groups, const double *resp,
                        int64_t lo, int64_t hi, int steps) {
-    k_move<F32, Scored, Periodic, Agg, Linear>
+    k_move<F32, Scored, Periodic, Agg, Linear, Currents>
         <<<grid_blocks(hi - lo), kBlock, 0, s_comp_>>>(
         d_planes_, d_planes32_, d_nbr_, grid_view_, d_s2c_, origin, dest,
         flying, weights, groups, ngroups, d_pos_, d_elem_, d_escaped_,
         d_flux_, d_lost_, d_lostrec_, d_loose_, lo, hi, loc_tol_, steps,
         mesh_.nelems, slices_ - 1, reflective, d_face_bc_, resp, nscores,
-        d_pidx_, d_pelem_, d_pshift_, d_inv_h_, d_moments_);
+        d_pidx_, d_pelem_, d_pshift_, d_inv_h_, d_moments_, d_cur_,
+        cur_keyed_);
     PT_HIP_CHECK(hipGetLastError());
   }
 
@@ -1386,11 +1516,12 @@ private:
                           int64_t n, int steps) {
     // Chunked launches: a ~2.6M-slot launch keeps each XCD's Morton-
     // contiguous slot range's mesh working set inside its private L2.
-    // Scored / periodic / wave-aggregated / linear moves take dedicated
-    // k_move instantiations; the plain (headline) instantiation compiles
-    // without any of those features.  Linear engines take the Linear twin
-    // of whichever instantiation the move would otherwise get (the
-    // wave-aggregated one under the same `agg` condition).
+    // Scored / periodic / wave-aggregated / linear / currents moves take
+    // dedicated k_move instantiations; the plain (headline) instantiation
+    // compiles without any of those features.  Linear engines take the
+    // Linear twin, face-current engines the Currents twin, of whichever
+    // instantiation the move would otherwise get (the wave-aggregated one
+    // under the same `agg` condition).
     const int64_t chunk = chunk_particles(n);
     const bool per = d_pidx_ != nullptr;
     // wave aggregation needs a single flat tally key per lane: plain
@@ -1400,11 +1531,11 @@ private:
       const int64_t hi = std::min(n, lo + chunk);
       using T = std::true_type;
       using F = std::false_type;
-      auto pick = [&](auto linc) {
+      auto pick = [&](auto linc, auto curc) {
         auto go = [&](auto f32c, auto scoredc, auto perc, auto aggc) {
           launch_move_one<decltype(f32c)::value, decltype(scoredc)::value,
                           decltype(perc)::value, decltype(aggc)::value,
-                          decltype(linc)::value>(
+                          decltype(linc)::value, decltype(curc)::value>(
               origin, dest, flying, weights, groups, resp, lo, hi, steps);
         };
         if (walk_fp32) {
@@ -1417,8 +1548,9 @@ private:
           else          per ? go(F{}, F{}, T{}, F{}) : go(F{}, F{}, F{}, F{});
         }
       };
-      if (linear) pick(T{});
-      else        pick(F{});
+      if (linear)             pick(T{}, F{});
+      else if (face_currents) pick(F{}, T{});
+      else                    pick(F{}, F{});
     }
   }
 
@@ -1515,6 +1647,10 @@ private:
   // Linear mode only (null otherwise): 1/heights, the un-sliced moments
   // [fsz_*4] and their end_batch running sum (allocated on first use).
   DeviceBuffer<double> d_inv_h_, d_moments_, d_msum_;
+  // Face currents only (null otherwise): the un-sliced currents [fsz_*4]
+  // and their end_batch sum / sum of squares (allocated on first use).
+  DeviceBuffer<double> d_cur_, d_csum_, d_csq_;
+  bool cur_keyed_ = false;
   DeviceBuffer<uint32_t> d_face_bc_;
   DeviceBuffer<int32_t> d_pidx_, d_pelem_;
   DeviceBuffer<double> d_pshift_;
@@ -1537,14 +1673,15 @@ private:
 
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
                                         int device, int ngroups, int nscores,
-                                        bool linear) {
+                                        bool linear, bool currents) {
+  check_tally_options(linear, currents);
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= device) {
     (void)hipGetLastError();
     return nullptr;
   }
   return std::make_unique<GpuEngine>(std::move(mesh), num_particles, device,
-                                     ngroups, nscores, linear);
+                                     ngroups, nscores, linear, currents);
 }
 
 } // namespace pumitally

@@ -45,20 +45,22 @@ struct PyEngine {
   bool gpu = false;
 
   PyEngine(const Mesh &mesh, int64_t n, const std::string &device,
-           int ngroups = 1, int nscores = 1, bool linear = false) {
+           int ngroups = 1, int nscores = 1, bool linear = false,
+           bool currents = false) {
     if (device == "cpu") {
-      eng = make_cpu_engine(mesh, n, ngroups, nscores, linear);
+      eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents);
     } else {
       int ordinal = 0;
       if (device.rfind("cuda:", 0) == 0) ordinal = std::stoi(device.substr(5));
       else if (device.rfind("gpu:", 0) == 0) ordinal = std::stoi(device.substr(4));
       else if (device != "cuda" && device != "gpu" && device != "auto")
         throw std::runtime_error("device must be cpu/cuda[:N]/auto");
-      eng = make_gpu_engine(mesh, n, ordinal, ngroups, nscores, linear);
+      eng = make_gpu_engine(mesh, n, ordinal, ngroups, nscores, linear,
+                            currents);
       if (eng) {
         gpu = true;
       } else if (device == "auto") {
-        eng = make_cpu_engine(mesh, n, ngroups, nscores, linear);
+        eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents);
       } else {
         // Fail loudly: a GPU was requested but none is usable.  GPU tests
         // must never fall back silently to the CPU oracle.
@@ -126,6 +128,25 @@ PYBIND11_MODULE(_core, m) {
                              })
       .def_property_readonly("volumes",
                              [](const Mesh &m_) { return vec_to_np(m_.volumes); })
+      .def_property_readonly("face_twins",
+                             // (nelems,4): flat index of the same face seen
+                             // from the neighbor (periodic: the paired
+                             // face); -1 on other boundary and cut faces
+                             [](const Mesh &m_) {
+                               const auto v = m_.face_twins();
+                               auto a = py::array_t<int64_t>({m_.nelems, (int64_t)4});
+                               std::memcpy(a.mutable_data(), v.data(),
+                                           v.size() * sizeof(int64_t));
+                               return a;
+                             })
+      .def_property_readonly("face_areas",
+                             [](const Mesh &m_) {
+                               const auto v = m_.face_areas();
+                               auto a = py::array_t<double>({m_.nelems, (int64_t)4});
+                               std::memcpy(a.mutable_data(), v.data(),
+                                           v.size() * sizeof(double));
+                               return a;
+                             })
       .def("centroid",
            [](const Mesh &m_, int32_t t) {
              const Vec3 c = m_.centroid(t);
@@ -689,12 +710,18 @@ PYBIND11_MODULE(_core, m) {
 
   py::class_<PyEngine>(m, "Engine")
       .def(py::init<const Mesh &, int64_t, const std::string &, int, int,
-                    bool>(),
+                    bool, bool>(),
            py::arg("mesh"), py::arg("num_particles"), py::arg("device") = "auto",
            py::arg("ngroups") = 1, py::arg("nscores") = 1,
-           py::arg("linear") = false)
+           py::arg("linear") = false, py::arg("currents") = false)
       .def_property_readonly("linear",
                              [](const PyEngine &e) { return e.eng->linear; })
+      .def_property_readonly(
+          "face_currents",
+          [](const PyEngine &e) { return e.eng->face_currents; })
+      // global boundary condition the engine snapshotted at construction
+      .def_property_readonly(
+          "reflective", [](const PyEngine &e) { return e.eng->reflective; })
       .def_property_readonly("ngroups",
                              [](const PyEngine &e) { return e.eng->ngroups; })
       .def_property_readonly("nscores",
@@ -947,6 +974,15 @@ PYBIND11_MODULE(_core, m) {
       .def("set_moments",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> m) {
              e.eng->set_moments(m.data(), (int64_t)m.size());
+           })
+      // face-current tallies (engine.h); all four throw RuntimeError on an
+      // engine built without currents=True
+      .def("currents", [](const PyEngine &e) { return vec_to_np(e.eng->currents()); })
+      .def("current_sum", [](const PyEngine &e) { return vec_to_np(e.eng->current_sum()); })
+      .def("current_sum_sq", [](const PyEngine &e) { return vec_to_np(e.eng->current_sum_sq()); })
+      .def("set_currents",
+           [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> j) {
+             e.eng->set_currents(j.data(), (int64_t)j.size());
            })
       .def("set_particle_state",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> pos,

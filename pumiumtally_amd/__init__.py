@@ -71,16 +71,29 @@ class TallyEngine:
     barycentric moments of every track (moments()), from which nodal_flux()
     and linear_coefficients() give a P1 field; flux() is unchanged by it.
     Off by default; fixed at construction.
+
+    currents=True additionally tallies, per (element, local face), the
+    weight of every tallied crossing that leaves the element through that
+    face (currents(): the outward partial current J+ integrated over the
+    face), from which net_current() and leakage() follow; flux() is
+    unchanged by it.  Off by default; fixed at construction
+    (face_currents tells); not available together with linear=True.
     """
 
     def __init__(self, mesh, num_particles: int, device: str = "auto",
-                 ngroups: int = 1, nscores: int = 1, linear: bool = False):
+                 ngroups: int = 1, nscores: int = 1, linear: bool = False,
+                 currents: bool = False):
+        if linear and currents:
+            raise ValueError(
+                "currents=True cannot be combined with linear=True "
+                "(not implemented)")
         self._eng = _core.Engine(mesh, num_particles, device, ngroups,
-                                 nscores, bool(linear))
+                                 nscores, bool(linear), bool(currents))
         self.mesh = mesh
         self.ngroups = ngroups
         self.nscores = nscores
         self.linear = bool(linear)
+        self.face_currents = bool(currents)
 
     @property
     def num_particles(self) -> int:
@@ -294,6 +307,118 @@ class TallyEngine:
         vol = np.asarray(self.mesh.volumes)[:, None]
         return (20.0 / vol) * (m - m.sum(axis=-1, keepdims=True) / 5.0)
 
+    # ---- face-current tallies; currents=True engines only ----
+
+    def _require_currents(self, what):
+        if not self.face_currents:
+            raise RuntimeError(
+                f"{what} needs face-current tallies: create the engine "
+                "with TallyEngine(..., currents=True)")
+
+    def currents(self):
+        """Outward partial currents of the current batch, shaped
+        flux().shape + (4,): currents()[..., e, f] is the summed weight of
+        the tallied tracks that left element e through its local face f
+        (the face opposite local vertex f; flat face index e*4+f as in
+        mesh.boundary_faces()).  No track length and no cosine enter; divide
+        by mesh.face_areas for a current density.  Groups and scores apply
+        exactly as for flux().  The final partial segment of a track counts
+        nothing; a reflective face records the outward crossing only."""
+        self._require_currents("currents()")
+        return self._eng.currents().reshape(self._tally_shape() + (4,))
+
+    def current_sum(self):
+        """Currents accumulated over the closed batches (end_batch() adds
+        the per-batch currents here and zeroes them); shaped like
+        currents()."""
+        self._require_currents("current_sum()")
+        return self._eng.current_sum().reshape(self._tally_shape() + (4,))
+
+    def current_sum_sq(self):
+        """Sum over the closed batches of the squared per-batch currents;
+        shaped like currents()."""
+        self._require_currents("current_sum_sq()")
+        return self._eng.current_sum_sq().reshape(self._tally_shape() + (4,))
+
+    def _face_classes(self):
+        """(twins (nelems*4,), reflective mask, vacuum mask) of the mesh's
+        faces as this engine treats them."""
+        import numpy as np
+
+        twins = np.asarray(self.mesh.face_twins).reshape(-1)
+        nbr = np.asarray(self.mesh.neighbors).reshape(-1)
+        boundary = (nbr == -1) & (twins < 0)
+        refl = np.zeros(nbr.size, dtype=bool)
+        if self._eng.reflective:      # global BC, fixed at construction
+            refl = boundary.copy()
+        else:
+            for fid in np.nonzero(boundary)[0]:
+                refl[fid] = self.mesh.face_is_reflective(int(fid))
+        return twins, refl, boundary & ~refl
+
+    def net_current(self, currents=None):
+        """Net outward current per (element, face), shaped like currents():
+        J[e, f] - J[twin of (e, f)].  On vacuum and partition-cut faces it
+        is J[e, f]; on reflective faces it is 0 (every crossing returns).
+        currents: optional array shaped like currents() (e.g.
+        current_sum()) to use instead of the current batch."""
+        import numpy as np
+
+        self._require_currents("net_current()")
+        j = self.currents() if currents is None else np.asarray(currents)
+        twins, refl, _ = self._face_classes()
+        flat = j.reshape(-1, twins.size)
+        has = twins >= 0
+        net = flat.copy()
+        net[:, has] -= flat[:, twins[has]]
+        net[:, refl] = 0.0
+        return net.reshape(j.shape)
+
+    def leakage(self, currents=None):
+        """Weight that left through the vacuum boundary: currents summed
+        over the vacuum boundary faces, per score and group (shape
+        flux().shape[:-1]; a scalar for ngroups=nscores=1)."""
+        import numpy as np
+
+        self._require_currents("leakage()")
+        j = self.currents() if currents is None else np.asarray(currents)
+        _, _, vac = self._face_classes()
+        flat = j.reshape(-1, vac.size)
+        out = flat[:, vac].sum(axis=1).reshape(j.shape[:-2])
+        return float(out) if out.ndim == 0 else out
+
+    def _element_leakage(self):
+        """(nscores, ngroups, nelems): per element, the currents summed over
+        its vacuum boundary faces."""
+        import numpy as np
+
+        _, _, vac = self._face_classes()
+        j = self.currents().reshape(self.nscores, self.ngroups,
+                                    self.mesh.nelems, 4)
+        return (j * vac.reshape(self.mesh.nelems, 4)).sum(axis=-1)
+
+    def _write_with_leakage(self, filename):
+        # The flux fields exactly as write_tally_results names them, each
+        # followed at the end by its leakage twin.
+        S, G, ne = self.nscores, self.ngroups, self.mesh.nelems
+        f = self.flux().reshape(S, G, ne)
+        lk = self._element_leakage()
+        flux_fields, leak_fields = [], []
+        for k in range(S):
+            name = "flux" if k == 0 else f"score{k}"
+            lname = "leakage" if k == 0 else f"leakage_score{k}"
+            flux_fields.append(
+                (name, _core.normalize_flux(self.mesh, f[k].sum(axis=0))))
+            leak_fields.append((lname, lk[k].sum(axis=0)))
+            if G > 1:
+                flux_fields += [(f"{name}_g{g}",
+                                 _core.normalize_flux(self.mesh, f[k, g]))
+                                for g in range(G)]
+                leak_fields += [(f"{lname}_g{g}", lk[k, g]) for g in range(G)]
+        if S == 1 and G == 1:
+            flux_fields.append(("volume", self.mesh.volumes))
+        self.mesh.write_vtk_fields(filename, flux_fields + leak_fields)
+
     def elem_ids(self):
         return self._eng.elem_ids()
 
@@ -354,6 +479,9 @@ class TallyEngine:
         self.synchronize()
         # linear engines add a "moments" key; everything else is unchanged
         extra = {"moments": self.moments()} if self.linear else {}
+        # ... and face-current engines a "currents" key
+        if self.face_currents:
+            extra["currents"] = self.currents()
         np.savez_compressed(
             path,
             flux=self.flux(),
@@ -376,6 +504,9 @@ class TallyEngine:
         if self.linear and "moments" in d.files:
             self._eng.set_moments(
                 np.ascontiguousarray(d["moments"], dtype=np.float64).ravel())
+        if self.face_currents and "currents" in d.files:
+            self._eng.set_currents(
+                np.ascontiguousarray(d["currents"], dtype=np.float64).ravel())
         self._eng.set_particle_state(
             np.ascontiguousarray(d["positions"], dtype=np.float64).ravel(),
             np.ascontiguousarray(d["elem_ids"], dtype=np.int32),
@@ -397,7 +528,14 @@ class TallyEngine:
     def write_tally_results(self, filename: str = "fluxresult.vtk"):
         """Write the normalized tally (legacy .vtk, or .vtu by extension).
         Linear engines additionally write the point field "nodal_flux"
-        (score 0 summed over groups, like the cell field "flux")."""
+        (score 0 summed over groups, like the cell field "flux").
+        Face-current engines additionally write one cell field "leakage"
+        per flux field (same name suffixes: leakage, leakage_g0, score1 ->
+        leakage_score1, ...): the element's currents summed over its vacuum
+        boundary faces, not normalized."""
+        if self.face_currents:
+            self._write_with_leakage(filename)
+            return
         points = []
         if self.linear:
             m0 = self.moments().reshape(self.nscores, self.ngroups,

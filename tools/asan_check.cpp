@@ -185,11 +185,60 @@ void threaded_linear_move() {
   if (e->moment_sum() != mo) abort();
 }
 
+// ... and with face currents on: per-thread partials must span the full
+// CURRENTS shape (4x the flux shape, scores included).  Destinations reach
+// outside the box so vacuum clips are booked too; integer weights and
+// responses make the sums exact.
+void threaded_currents_move() {
+  Mesh m = build_box(6, 6, 6, 1.0, 1.0, 1.0);
+  const int64_t n = 70000;
+  const int G = 2, S = 2;
+  auto e = make_cpu_engine(m, n, G, S, /*linear=*/false, /*currents=*/true);
+  std::mt19937_64 rng(23);
+  std::uniform_real_distribution<double> u(0.02, 0.98), v(-0.2, 1.2);
+  std::vector<double> o(n * 3), d(n * 3), w(n), resp(n * S);
+  std::vector<int8_t> fly(n, 1);
+  std::vector<uint16_t> grp(n);
+  for (int64_t i = 0; i < n * 3; ++i) { o[i] = u(rng); d[i] = v(rng); }
+  for (int64_t i = 0; i < n; ++i) { w[i] = 1 + rng() % 4; grp[i] = rng() % G; }
+  for (int64_t i = 0; i < n * S; ++i) resp[i] = 1 + rng() % 3;
+  e->copy_initial_position(o.data(), n);
+  e->move(o.data(), d.data(), fly.data(), w.data(), n, grp.data(),
+          resp.data());
+  // leakage of score 0 == escaped weight * its response, exactly
+  const std::vector<uint8_t> esc = e->escaped();
+  double want = 0.0, got = 0.0;
+  for (int64_t i = 0; i < n; ++i)
+    if (esc[i]) want += w[i] * resp[i * S];
+  std::vector<double> cu = e->currents();
+  if (cu.size() != e->flux().size() * 4) abort();
+  for (int g = 0; g < G; ++g)
+    for (int64_t t = 0; t < m.nelems; ++t)
+      for (int f = 0; f < 4; ++f)
+        if (m.nbr[t * 4 + f] == -1) got += cu[(g * m.nelems + t) * 4 + f];
+  if (want <= 0.0 || got != want) abort();
+  std::vector<int32_t> el = e->elem_ids(), oe(n);
+  std::vector<double> pos = e->positions(), op(n * 3);
+  std::vector<int8_t> st(n);
+  // particles now sit at pos in el: walk them back with walk_raw
+  e->walk_raw(n, pos.data(), o.data(), el.data(), w.data(), op.data(),
+              oe.data(), st.data(), grp.data(), resp.data());
+  cu = e->currents();
+  e->end_batch();
+  if (e->current_sum() != cu) abort();
+  const std::vector<double> sq = e->current_sum_sq();
+  for (size_t i = 0; i < cu.size(); ++i)
+    if (sq[i] != cu[i] * cu[i]) abort();
+  for (double x : e->currents())
+    if (x != 0.0) abort();
+}
+
 int main() {
   golden();
   fuzz();
   threaded_scored_move();
   threaded_linear_move();
+  threaded_currents_move();
   // the CPU stateful partitioned engine: step() and step_local() with
   // resampled origins, against the replicated engine
   if (partition_cpu_scenario() != 0) abort();
