@@ -1,6 +1,7 @@
 // Serial CPU engine: the correctness oracle for the HIP engine and the
 // no-GPU plumbing path (BASELINE config 1).
 #include "engine.h"
+#include "tally_sink.h"
 #include "walk.h"
 
 #include <atomic>
@@ -8,6 +9,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <thread>
+#include <type_traits>
 
 namespace pumitally {
 
@@ -29,6 +31,15 @@ std::vector<double> normalize_flux(const Mesh &m, const std::vector<double> &flu
 namespace {
 
 class CpuEngine final : public Engine {
+  // Where one thread's contributions land: the engine's arrays on the
+  // serial path, that thread's partials on the threaded one.
+  struct Tallies {
+    double *flux, *moments, *currents;
+  };
+  struct Counts {
+    int64_t lost = 0, reloc = 0;
+  };
+
 public:
   CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin, bool cur)
       : mesh_(std::move(mesh)), n_(n) {
@@ -95,70 +106,18 @@ public:
             const double *responses = nullptr) override {
     check_n(n);
     const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
-    // Thread-parallel over particles for large batches (the reference's CPU
-    // path is Kokkos OpenMP).  Each thread tallies into a private flux
-    // array; partials are summed in thread-index order, so results are
-    // DETERMINISTIC for a fixed thread count (and exactly serial-order for
-    // one thread).  Small batches stay serial for bitwise stability of the
-    // golden tests.
     unsigned hw = std::thread::hardware_concurrency();
     if (const char *env = getenv("PUMITALLY_CPU_THREADS")) {
       const int v = atoi(env);
       hw = v > 0 ? (unsigned)v : 1;
     }
-    const int nthreads =
-        (n >= 65536 && hw > 1) ? (int)std::min<unsigned>(hw, 64) : 1;
-    if (nthreads > 1) {
-      // full tally shape INCLUDING the score dimension: the scored add
-      // writes k*ngroups*nelems + group*nelems + elem for k < nscores
-      // (an nelems*ngroups-sized partial overflows the heap -- found by
-      // tools/part_world2_soak at 400k particles with nscores=2)
-      std::vector<std::vector<double>> partial(
-          nthreads, std::vector<double>(flux_.size(), 0.0));
-      // ... and, in linear mode, a moments partial of the full moments
-      // shape (4x the flux shape; empty otherwise, never written then)
-      std::vector<std::vector<double>> partial_m(
-          nthreads, std::vector<double>(moments_.size(), 0.0));
-      // ... and, with face currents on, a partial of the full currents
-      // shape (scores included, like the flux partial above)
-      std::vector<std::vector<double>> partial_c(
-          nthreads, std::vector<double>(currents_.size(), 0.0));
-      std::atomic<int64_t> lost{0}, reloc{0};
-      std::vector<std::thread> workers;
-      const int64_t per = (n + nthreads - 1) / nthreads;
-      for (int t = 0; t < nthreads; ++t) {
-        workers.emplace_back([&, t] {
-          const int64_t lo = t * per, hi = std::min<int64_t>(n, lo + per);
-          int64_t my_lost = 0, my_reloc = 0;
-          for (int64_t i = lo; i < hi; ++i)
-            move_one(origin, dest, flying, weights, groups, responses, i,
-                     steps, partial[t].data(), partial_m[t].data(),
-                     partial_c[t].data(), my_lost, my_reloc);
-          lost += my_lost;
-          reloc += my_reloc;
+    const Counts c =
+        for_each_particle(n, hw, [&](int64_t i, const Tallies &out, Counts &k) {
+          move_one(origin, dest, flying, weights, groups, responses, i, steps,
+                   out, k);
         });
-      }
-      for (auto &w : workers) w.join();
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < flux_.size(); ++e)
-          flux_[e] += partial[t][e];
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < moments_.size(); ++e)
-          moments_[e] += partial_m[t][e];
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < currents_.size(); ++e)
-          currents_[e] += partial_c[t][e];
-      stats_.lost_particles += lost.load();
-      stats_.relocated += reloc.load();
-      stats_.moves++;
-      return;
-    }
-    int64_t lost = 0, reloc = 0;
-    for (int64_t i = 0; i < n; ++i)
-      move_one(origin, dest, flying, weights, groups, responses, i, steps,
-               flux_.data(), moments_.data(), currents_.data(), lost, reloc);
-    stats_.lost_particles += lost;
-    stats_.relocated += reloc;
+    stats_.lost_particles += c.lost;
+    stats_.relocated += c.reloc;
     stats_.moves++;
   }
 
@@ -167,8 +126,7 @@ public:
   void move_one(const double *origin, const double *dest,
                 const int8_t *flying, const double *weights,
                 const uint16_t *groups, const double *responses, int64_t i,
-                int steps, double *flux_out, double *mom_out, double *cur_out,
-                int64_t &lost, int64_t &reloc) {
+                int steps, const Tallies &out, Counts &counts) {
     if (!flying[i]) return;
     Vec3 o{pos_[i * 3], pos_[i * 3 + 1], pos_[i * 3 + 2]};
     if (origin && !escaped_[i]) {
@@ -178,7 +136,7 @@ public:
         elem_[i] = mesh_.locate(q, loc_tol_, &loose);
         if (loose) loose_++; // rare; atomic is fine in the threaded path
         o = q;
-        reloc++;
+        counts.reloc++;
       }
     }
     if (elem_[i] < 0) {
@@ -192,57 +150,27 @@ public:
     int32_t out_elem;
     Vec3 out_pos;
     bool out_esc;
-    const int64_t goff =
-        groups ? (int64_t)(groups[i] % ngroups) * mesh_.nelems : 0;
-    const int64_t gsz = (int64_t)ngroups * mesh_.nelems;
-    const double *resp = responses ? responses + i * nscores : nullptr;
-    auto add = [&](int32_t e, double v) {
-      if (!resp) {
-        flux_out[goff + e] += v;
-        return;
-      }
-      for (int k = 0; k < nscores; ++k)
-        flux_out[k * gsz + goff + e] += v * resp[k];
-    };
-    const uint32_t *bc =
-        mesh_.face_bc_bits.empty() ? nullptr : mesh_.face_bc_bits.data();
-    const int32_t *pix =
-        mesh_.periodic_idx.empty() ? nullptr : mesh_.periodic_idx.data();
-    auto walk = [&](auto &tally) {
-      if (walk_fp32)
-        walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
-                             mesh_.nbr.data(), elem_[i], o, d, weights[i],
-                             steps, tally, &out_elem, &out_pos, &out_esc,
-                             reflective, bc, pix, mesh_.periodic_elem.data(),
-                             mesh_.periodic_shift.data());
-      else
-        walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem_[i], o,
-                           d, weights[i], steps, tally, &out_elem, &out_pos,
-                           &out_esc, reflective, bc, pix,
-                           mesh_.periodic_elem.data(),
-                           mesh_.periodic_shift.data());
-    };
-    if (linear) {
-      auto add_lin = [&](int32_t e, double t0, double t1, const WalkState &s) {
-        add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
-      };
-      walk(add_lin);
-    } else if (face_currents) {
-      // an escaped particle leaving again where it sits is one departure
-      // (walk.h walk_current_face)
-      bool reexit = escaped_[i] != 0;
-      auto add_cur = [&](int32_t e, double t0, double t1, const WalkState &s,
-                         int exit_face) {
-        const int face = walk_current_face<true>(
-            reexit, mesh_.nbr.data(), e, exit_face, t1, reflective, bc, pix);
-        add_current(flux_out, cur_out, goff, gsz, resp, e, t0, t1, s, face);
-      };
-      walk(add_cur);
-    } else {
-      walk(add);
-    }
+    const TallyMesh tm = tally_mesh();
+    // an escaped particle leaving again where it sits is one departure
+    // (walk.h walk_current_face)
+    tally_walk</*ReexitRule=*/true>(
+        out, groups, responses, i, tm, escaped_[i] != 0, [&](auto &sink) {
+          if (walk_fp32)
+            walk_segment32<true>(tm.planes, mesh_.planes32.data(), tm.nbr,
+                                 elem_[i], o, d, weights[i], steps, sink,
+                                 &out_elem, &out_pos, &out_esc, reflective,
+                                 tm.face_bc, tm.pidx,
+                                 mesh_.periodic_elem.data(),
+                                 mesh_.periodic_shift.data());
+          else
+            walk_segment<true>(tm.planes, tm.nbr, elem_[i], o, d, weights[i],
+                               steps, sink, &out_elem, &out_pos, &out_esc,
+                               reflective, tm.face_bc, tm.pidx,
+                               mesh_.periodic_elem.data(),
+                               mesh_.periodic_shift.data());
+        });
     if (out_elem == kWalkLost) {
-      lost++;
+      counts.lost++;
       record_lost(i, out_pos);
       out_elem = elem_[i];
     }
@@ -264,50 +192,16 @@ public:
                 double *out_t = nullptr,
                 int32_t *out_prev = nullptr) override {
     const int steps = max_steps > 0 ? max_steps : default_max_steps(mesh_);
-    const unsigned hw = std::thread::hardware_concurrency();
-    if (n >= 65536 && hw > 1) {
-      const int nthreads = (int)std::min<unsigned>(hw, 64);
-      std::vector<std::vector<double>> partial(
-          nthreads, std::vector<double>(flux_.size(), 0.0));
-      std::vector<std::vector<double>> partial_m(
-          nthreads, std::vector<double>(moments_.size(), 0.0));
-      std::vector<std::vector<double>> partial_c(
-          nthreads, std::vector<double>(currents_.size(), 0.0));
-      std::atomic<int64_t> lost{0};
-      std::vector<std::thread> workers;
-      const int64_t per = (n + nthreads - 1) / nthreads;
-      for (int t = 0; t < nthreads; ++t) {
-        workers.emplace_back([&, t] {
-          const int64_t lo = t * per, hi = std::min<int64_t>(n, lo + per);
-          int64_t my_lost = 0;
-          for (int64_t i = lo; i < hi; ++i)
-            walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
-                         out_elem, out_status, out_dest, in_t, in_prev,
-                         out_o, out_t, out_prev, i, steps,
-                         partial[t].data(), partial_m[t].data(),
-                         partial_c[t].data(), my_lost);
-          lost += my_lost;
+    // PUMITALLY_CPU_THREADS is move()'s switch; walk_raw threads on the
+    // hardware count alone
+    const Counts c = for_each_particle(
+        n, std::thread::hardware_concurrency(),
+        [&](int64_t i, const Tallies &out, Counts &k) {
+          walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
+                       out_elem, out_status, out_dest, in_t, in_prev, out_o,
+                       out_t, out_prev, i, steps, out, k);
         });
-      }
-      for (auto &w : workers) w.join();
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < flux_.size(); ++e) flux_[e] += partial[t][e];
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < moments_.size(); ++e)
-          moments_[e] += partial_m[t][e];
-      for (int t = 0; t < nthreads; ++t)
-        for (size_t e = 0; e < currents_.size(); ++e)
-          currents_[e] += partial_c[t][e];
-      stats_.lost_particles += lost.load();
-      return;
-    }
-    int64_t lost = 0;
-    for (int64_t i = 0; i < n; ++i)
-      walk_raw_one(pos, dest, elem, weights, groups, responses, out_pos,
-                   out_elem, out_status, out_dest, in_t, in_prev, out_o,
-                   out_t, out_prev, i, steps, flux_.data(), moments_.data(),
-                   currents_.data(), lost);
-    stats_.lost_particles += lost;
+    stats_.lost_particles += c.lost;
   }
 
   void walk_raw_one(const double *pos, const double *dest,
@@ -317,30 +211,14 @@ public:
                     double *out_dest, const double *in_t,
                     const int32_t *in_prev, double *out_o, double *out_t,
                     int32_t *out_prev, int64_t i, int steps,
-                    double *flux_out, double *mom_out, double *cur_out,
-                    int64_t &lost) {
+                    const Tallies &out, Counts &counts) {
     {
       const Vec3 o{pos[i * 3], pos[i * 3 + 1], pos[i * 3 + 2]};
       const Vec3 d{dest[i * 3], dest[i * 3 + 1], dest[i * 3 + 2]};
       int32_t oe;
       Vec3 op;
       bool esc;
-      const int64_t goff =
-          groups ? (int64_t)(groups[i] % ngroups) * mesh_.nelems : 0;
-      const int64_t gsz = (int64_t)ngroups * mesh_.nelems;
-      const double *resp = responses ? responses + i * nscores : nullptr;
-      auto add = [&](int32_t e, double v) {
-        if (!resp) {
-          flux_out[goff + e] += v;
-          return;
-        }
-        for (int k = 0; k < nscores; ++k)
-          flux_out[k * gsz + goff + e] += v * resp[k];
-      };
-      const uint32_t *bc =
-          mesh_.face_bc_bits.empty() ? nullptr : mesh_.face_bc_bits.data();
-      const int32_t *pix =
-          mesh_.periodic_idx.empty() ? nullptr : mesh_.periodic_idx.data();
+      const TallyMesh tm = tally_mesh();
       Vec3 od{d.x, d.y, d.z};
       const double rt = in_t ? in_t[i] : 0.0;
       const int32_t rp = in_prev ? in_prev[i] : -1;
@@ -350,45 +228,31 @@ public:
       // Resumed walks (in_t / in_prev) need nothing extra for the moments:
       // in_t only seeds t_cur, pos is the wrap-segment origin the sender
       // exported, so (o, d, seg_len) -- all tet_moments reads besides
-      // [t0, t1] -- are the uncut walk's.
-      auto walk = [&](auto &tally) {
-        if (walk_fp32)
-          walk_segment32<true>(mesh_.planes.data(), mesh_.planes32.data(),
-                               mesh_.nbr.data(), elem[i], o, d, weights[i],
-                               steps, tally, &oe, &op, &esc, reflective, bc,
-                               pix, mesh_.periodic_elem.data(),
-                               mesh_.periodic_shift.data(), &od, rt, rp, &oo,
-                               &ot, &opv);
-        else
-          walk_segment<true>(mesh_.planes.data(), mesh_.nbr.data(), elem[i],
-                             o, d, weights[i], steps, tally, &oe, &op, &esc,
-                             reflective, bc, pix, mesh_.periodic_elem.data(),
-                             mesh_.periodic_shift.data(), &od, rt, rp, &oo,
-                             &ot, &opv);
-      };
-      if (linear) {
-        auto add_lin = [&](int32_t e, double t0, double t1,
-                           const WalkState &s) {
-          add_linear(flux_out, mom_out, goff, gsz, resp, e, t0, t1, s);
-        };
-        walk(add_lin);
-      } else if (face_currents) {
-        // A resumed walk starts inside its element, so the crossing its
-        // sender counted is not counted again.
-        auto add_cur = [&](int32_t e, double t0, double t1,
-                           const WalkState &s, int exit_face) {
-          add_current(flux_out, cur_out, goff, gsz, resp, e, t0, t1, s,
-                      exit_face);
-        };
-        walk(add_cur);
-      } else {
-        walk(add);
-      }
+      // [t0, t1] -- are the uncut walk's.  For the currents, a resumed walk
+      // starts inside its element, so the crossing its sender counted is not
+      // counted again; there is no particle state and no re-exit rule.
+      tally_walk</*ReexitRule=*/false>(
+          out, groups, responses, i, tm, false, [&](auto &sink) {
+            if (walk_fp32)
+              walk_segment32<true>(tm.planes, mesh_.planes32.data(), tm.nbr,
+                                   elem[i], o, d, weights[i], steps, sink, &oe,
+                                   &op, &esc, reflective, tm.face_bc, tm.pidx,
+                                   mesh_.periodic_elem.data(),
+                                   mesh_.periodic_shift.data(), &od, rt, rp,
+                                   &oo, &ot, &opv);
+            else
+              walk_segment<true>(tm.planes, tm.nbr, elem[i], o, d, weights[i],
+                                 steps, sink, &oe, &op, &esc, reflective,
+                                 tm.face_bc, tm.pidx,
+                                 mesh_.periodic_elem.data(),
+                                 mesh_.periodic_shift.data(), &od, rt, rp, &oo,
+                                 &ot, &opv);
+          });
       int8_t st = 0;
       if (oe == kWalkLost) {
         st = 3;
         oe = elem[i];
-        lost++;
+        counts.lost++;
         record_lost(i, op);
       } else if (esc) {
         st = 1;
@@ -523,47 +387,95 @@ private:
     if (n != n_) throw std::runtime_error("particle count mismatch");
   }
 
-  // Linear-mode contribution (rich walk callback): the flux add is the
-  // plain path's expression and order, so flux stays bit-identical to a
-  // non-linear engine's; the 4 moments land next to each other at
-  // (flux index)*4.
-  void add_linear(double *flux_out, double *mom_out, int64_t goff,
-                  int64_t gsz, const double *resp, int32_t e, double t0,
-                  double t1, const WalkState &s) const {
-    const double v = (t1 - t0) * s.seg_len * s.weight;
-    double m[4];
-    tet_moments(mesh_.planes.data() + (int64_t)e * 4,
-                mesh_.inv_heights.data() + (int64_t)e * 4, s, t0, t1, v, m);
-    if (!resp) {
-      flux_out[goff + e] += v;
-      for (int f = 0; f < 4; ++f) mom_out[(goff + e) * 4 + f] += m[f];
-      return;
+  // Runs one(i, tallies, counts) for every particle i in [0, n).
+  // Thread-parallel over particles for large batches (the reference's CPU
+  // path is Kokkos OpenMP), on up to `hw` threads.  Each thread tallies into
+  // private partials; they are summed in thread-index order, so results are
+  // DETERMINISTIC for a fixed thread count (and exactly serial-order for one
+  // thread).  Small batches stay serial for bitwise stability of the golden
+  // tests.
+  template <class One>
+  Counts for_each_particle(int64_t n, unsigned hw, One one) {
+    Counts total;
+    const int nthreads =
+        (n >= 65536 && hw > 1) ? (int)std::min<unsigned>(hw, 64) : 1;
+    if (nthreads == 1) {
+      const Tallies out{flux_.data(), moments_.data(), currents_.data()};
+      for (int64_t i = 0; i < n; ++i) one(i, out, total);
+      return total;
     }
-    for (int k = 0; k < nscores; ++k) {
-      flux_out[k * gsz + goff + e] += v * resp[k];
-      for (int f = 0; f < 4; ++f)
-        mom_out[(k * gsz + goff + e) * 4 + f] += m[f] * resp[k];
+    // Every partial has its array's FULL shape, score dimension included:
+    // the scored add writes k*ngroups*nelems + group*nelems + elem for
+    // k < nscores (an nelems*ngroups-sized partial overflows the heap --
+    // found by tools/part_world2_soak at 400k particles with nscores=2).
+    // Moments and currents are 4x the flux shape, or empty (and never
+    // written) when the engine does not tally them.
+    std::vector<double> *const arrays[3] = {&flux_, &moments_, &currents_};
+    std::vector<std::vector<double>> partial[3];
+    for (int a = 0; a < 3; ++a)
+      partial[a].assign(nthreads, std::vector<double>(arrays[a]->size(), 0.0));
+    std::vector<Counts> counts(nthreads);
+    std::vector<std::thread> workers;
+    const int64_t per = (n + nthreads - 1) / nthreads;
+    for (int t = 0; t < nthreads; ++t) {
+      workers.emplace_back([&, t] {
+        const int64_t lo = t * per, hi = std::min<int64_t>(n, lo + per);
+        const Tallies out{partial[0][t].data(), partial[1][t].data(),
+                          partial[2][t].data()};
+        Counts mine;
+        for (int64_t i = lo; i < hi; ++i) one(i, out, mine);
+        counts[t] = mine;
+      });
     }
+    for (auto &w : workers) w.join();
+    for (int a = 0; a < 3; ++a)
+      for (int t = 0; t < nthreads; ++t)
+        for (size_t e = 0; e < arrays[a]->size(); ++e)
+          (*arrays[a])[e] += partial[a][t][e];
+    for (const Counts &c : counts) {
+      total.lost += c.lost;
+      total.reloc += c.reloc;
+    }
+    return total;
   }
 
-  // Face-current contribution (face walk callback): the flux add is the
-  // plain path's expression and order, so flux stays bit-identical to an
-  // engine without the option; a crossing (exit_face >= 0) adds the weight
-  // at (flux index)*4 + exit_face.
-  void add_current(double *flux_out, double *cur_out, int64_t goff,
-                   int64_t gsz, const double *resp, int32_t e, double t0,
-                   double t1, const WalkState &s, int exit_face) const {
-    const double v = (t1 - t0) * s.seg_len * s.weight;
-    if (!resp) {
-      flux_out[goff + e] += v;
-      if (exit_face >= 0) cur_out[(goff + e) * 4 + exit_face] += s.weight;
-      return;
-    }
-    for (int k = 0; k < nscores; ++k) {
-      flux_out[k * gsz + goff + e] += v * resp[k];
-      if (exit_face >= 0)
-        cur_out[(k * gsz + goff + e) * 4 + exit_face] += s.weight * resp[k];
-    }
+  TallyMesh tally_mesh() const {
+    return {mesh_.planes.data(),
+            mesh_.inv_heights.data(),
+            mesh_.nbr.data(),
+            mesh_.face_bc_bits.empty() ? nullptr : mesh_.face_bc_bits.data(),
+            mesh_.periodic_idx.empty() ? nullptr : mesh_.periodic_idx.data(),
+            reflective};
+  }
+
+  // Builds particle i's tally sink (tally_sink.h) for the engine's mode, with
+  // plain += into `out`, and hands it to walk(sink).
+  template <bool ReexitRule, class Walk>
+  void tally_walk(const Tallies &out, const uint16_t *groups,
+                  const double *responses, int64_t i, const TallyMesh &tm,
+                  bool reexit, Walk walk) const {
+    auto go = [&](auto mode, double *companion) {
+      TallySink<decltype(mode)::value, /*Scored=*/true, PlainAdder<HostPlus>,
+                ReexitRule, /*Periodic=*/true>
+          sink{{},
+               out.flux,
+               companion,
+               tally_group_offset(groups, i, ngroups, mesh_.nelems),
+               (int64_t)ngroups * mesh_.nelems,
+               responses,
+               i,
+               nscores,
+               tm,
+               reexit};
+      walk(sink);
+    };
+    using M = TallyMode;
+    if (linear)
+      go(std::integral_constant<M, M::Linear>{}, out.moments);
+    else if (face_currents)
+      go(std::integral_constant<M, M::Currents>{}, out.currents);
+    else
+      go(std::integral_constant<M, M::Flux>{}, nullptr);
   }
 
   void record_lost(int64_t i, Vec3 p) {

@@ -32,6 +32,7 @@
 //     steady-state step, results unchanged.
 #include "../core/engine.h"
 #include "../core/origin_delta.h"
+#include "../core/tally_sink.h"
 #include "../core/walk.h"
 #include "hip_util.h"
 
@@ -234,13 +235,26 @@ __global__ void k_reduce_slices(double *__restrict__ flux, int64_t nelems,
 // atomicAdd per run (the run tail carries the total).  Runs are maximal
 // CONTIGUOUS ACTIVE lane spans with equal el: a gap in the active mask
 // starts a new run, so shuffles never read across inactive lanes.
-__device__ __forceinline__ void wave_agg_atomic_add(double *__restrict__ flux,
-                                                    int32_t el, double v) {
+//
+// wave_run_sum does the reduction over any number of values that share one
+// key (one for the flux or a keyed current, five for the flux plus the four
+// moments of a Linear crossing): the run structure (heads, tails) depends
+// only on the key and the active mask, so it is computed ONCE however many
+// values ride on it.  The run's tail lane then calls tail(totals...).
+__device__ __forceinline__ void wave_run_step(double &acc, int off, int lane,
+                                              int head_lane) {
+  const double up = __shfl_up(acc, off);
+  if (lane - off >= head_lane) acc += up;
+}
+
+template <class Tail, class... Acc>
+__device__ __forceinline__ void wave_run_sum(int32_t key, Tail tail,
+                                             Acc... acc) {
   const unsigned long long mask = __ballot(1);
   const int lane = (int)(threadIdx.x & 63u);
-  const int32_t prev_el = __shfl_up(el, 1);
+  const int32_t prev_key = __shfl_up(key, 1);
   const bool prev_active = lane > 0 && ((mask >> (lane - 1)) & 1ull);
-  const bool head = !prev_active || prev_el != el;
+  const bool head = !prev_active || prev_key != key;
   // inclusive max-scan of head lane indices: every lane learns its run head
   int head_lane = head ? lane : 0;
 #pragma unroll
@@ -251,57 +265,81 @@ __device__ __forceinline__ void wave_agg_atomic_add(double *__restrict__ flux,
   }
   // inclusive segmented sum over the run (all source lanes inside the run
   // are active and contiguous by construction)
-  double acc = v;
 #pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double up = __shfl_up(acc, off);
-    if (lane - off >= head_lane) acc += up;
-  }
-  const int32_t next_el = __shfl_down(el, 1);
+  for (int off = 1; off < 64; off <<= 1)
+    (wave_run_step(acc, off, lane, head_lane), ...);
+  const int32_t next_key = __shfl_down(key, 1);
   const bool next_active = lane < 63 && ((mask >> (lane + 1)) & 1ull);
-  if (!next_active || next_el != el) atomicAdd(&flux[el], acc);
+  if (!next_active || next_key != key) tail(acc...);
 }
 
-// Linear-mode form of the above: the run structure (heads, tails) depends
-// only on el and the active mask, so it is computed ONCE and the segmented
-// sum is run over five values -- the flux contribution and the crossing's
-// four moments.  The run tail issues one atomic per component: flux[el]
-// and the 32-byte span moments[4*el .. 4*el+3].  (How the memory side
-// treats a 32-byte atomic span is unmeasured; nothing here relies on it.)
-__device__ __forceinline__ void
-wave_agg_atomic_add_linear(double *__restrict__ flux,
-                           double *__restrict__ moments, int32_t el, double v,
-                           const double (&m)[4]) {
-  const unsigned long long mask = __ballot(1);
-  const int lane = (int)(threadIdx.x & 63u);
-  const int32_t prev_el = __shfl_up(el, 1);
-  const bool prev_active = lane > 0 && ((mask >> (lane - 1)) & 1ull);
-  const bool head = !prev_active || prev_el != el;
-  int head_lane = head ? lane : 0;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(head_lane, off);
-    if (lane >= off && ((mask >> (lane - off)) & 1ull) && up > head_lane)
-      head_lane = up;
+// The adder policies of the tally sink (core/tally_sink.h) on the device:
+// one atomicAdd per value ...
+struct AtomicPlus {
+  __device__ __forceinline__ void operator()(double *p, double v) const {
+    atomicAdd(p, v);
   }
-  double acc[5] = {v, m[0], m[1], m[2], m[3]};
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const bool take = lane - off >= head_lane;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const double up = __shfl_up(acc[c], off);
-      if (take) acc[c] += up;
+};
+using AtomicAdder = PlainAdder<AtomicPlus>;
+
+// ... or, for unscored, ungrouped moves under wave aggregation (the flux
+// index is then the element id, an int32 key), one atomicAdd per run: the
+// flux through wave_run_sum; a Linear crossing's flux and four moments
+// through ONE five-value reduction, the tail issuing flux[el] and the
+// 32-byte span moments[4*el .. 4*el+3] (how the memory side treats a
+// 32-byte atomic span is unmeasured; nothing here relies on it); a current
+// as one plain atomicAdd per crossing (default), or with `cur_keyed` the
+// same run aggregation keyed on the flat face index el*4+f, which the engine
+// enables only while nelems*4 fits an int32.
+struct WaveAdder {
+  static constexpr bool kFusedMoments = true;
+  bool cur_keyed;
+  __device__ __forceinline__ void flux(double *__restrict__ flux, int64_t at,
+                                       double v) const {
+    const int32_t el = (int32_t)at;
+    wave_run_sum(el, [&](double sum) { atomicAdd(&flux[el], sum); }, v);
+  }
+  __device__ __forceinline__ void moments(double *__restrict__ flux,
+                                          double *__restrict__ mom, int64_t at,
+                                          double v,
+                                          const double (&m)[4]) const {
+    const int32_t el = (int32_t)at;
+    wave_run_sum(
+        el,
+        [&](double sum, double m0, double m1, double m2, double m3) {
+          atomicAdd(&flux[el], sum);
+          double *mo = mom + (int64_t)el * 4;
+          atomicAdd(&mo[0], m0);
+          atomicAdd(&mo[1], m1);
+          atomicAdd(&mo[2], m2);
+          atomicAdd(&mo[3], m3);
+        },
+        v, m[0], m[1], m[2], m[3]);
+  }
+  // a current, at4 = el*4 + face
+  __device__ __forceinline__ void companion(double *__restrict__ cur,
+                                            int64_t at4, double w) const {
+    if (cur_keyed) {
+      const int32_t key = (int32_t)at4;
+      wave_run_sum(key, [&](double sum) { atomicAdd(&cur[key], sum); }, w);
+    } else {
+      atomicAdd(&cur[at4], w);
     }
   }
-  const int32_t next_el = __shfl_down(el, 1);
-  const bool next_active = lane < 63 && ((mask >> (lane + 1)) & 1ull);
-  if (!next_active || next_el != el) {
-    atomicAdd(&flux[el], acc[0]);
-    double *mo = moments + (int64_t)el * 4;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) atomicAdd(&mo[f], acc[1 + f]);
-  }
+};
+
+// The kernels' <Linear, Currents> switches as a sink mode.
+template <bool Linear, bool Currents>
+constexpr TallyMode kernel_tally_mode =
+    Linear ? TallyMode::Linear
+           : (Currents ? TallyMode::Currents : TallyMode::Flux);
+
+template <bool Wave>
+__device__ __forceinline__ auto make_adder(bool cur_keyed) {
+  if constexpr (Wave)
+    return WaveAdder{cur_keyed};
+  else
+    return AtomicAdder{};
 }
 
 // Face currents under the aggregated dispatch: plain atomics (default) or
@@ -340,11 +378,13 @@ inline bool wave_agg() {
 //
 // Currents=true (never together with Linear) additionally adds the weight
 // of every crossing to `cur` at (flux index)*4 + exit face -- ONE un-sliced
-// array like the moments.  Under Agg the flux still goes through
-// wave_agg_atomic_add first thing in the callback, i.e. with the active set
-// the non-currents kernel has there; the current is one plain atomicAdd per
-// crossing, or with cur_keyed the same run aggregation keyed on el*4+f.
+// array like the moments.  Under Agg the flux still goes through the run
+// aggregation first thing in the callback, i.e. with the active set the
+// non-currents kernel has there; the current follows (WaveAdder::current).
 // Currents=false instantiations never read cur / cur_keyed.
+//
+// What a crossing contributes, and where, is the tally sink's business
+// (core/tally_sink.h); the kernel only picks its mode and adder.
 template <bool F32, bool Scored = false, bool Periodic = false,
           bool Agg = false, bool Linear = false, bool Currents = false>
 __global__ void k_move(const Plane *__restrict__ planes,
@@ -381,6 +421,8 @@ __global__ void k_move(const Plane *__restrict__ planes,
   // codegen identical to before those features existed.
   flux += (int64_t)(blockIdx.x & (unsigned)slice_mask) * nelems * ngroups *
           (Scored ? nscores : 1);
+  constexpr TallyMode Mode = kernel_tally_mode<Linear, Currents>;
+  const TallyMesh tmesh{planes, inv_h, nbr, face_bc, pidx, reflective};
   const unsigned bpx = gridDim.x / 8u;
   const unsigned vb = (blockIdx.x % 8u) * bpx + blockIdx.x / 8u;
   const int64_t m = hi - lo;
@@ -413,95 +455,20 @@ __global__ void k_move(const Plane *__restrict__ planes,
     int32_t out_elem;
     Vec3 out_pos;
     bool out_esc;
+    // Wave aggregation is dispatched only when groups==nullptr, so the group
+    // offset is 0 for every lane and the element id alone is the key.
+    constexpr bool Wave = Agg && !Scored;
     const int64_t goff =
-        groups ? (int64_t)(groups[c] % ngroups) * nelems : 0;
-    auto add = [&](int32_t el, double v) {
-      if constexpr (Scored) {
-        const int64_t gsz = (int64_t)ngroups * nelems;
-        if (resp) {
-          for (int k = 0; k < nscores; ++k)
-            atomicAdd(&flux[k * gsz + goff + el], v * resp[c * nscores + k]);
-        } else {
-          atomicAdd(&flux[goff + el], v);
-        }
-      } else if constexpr (Agg) {
-        // dispatched only when groups==nullptr, so goff==0 for every lane
-        // and el alone is the aggregation key
-        wave_agg_atomic_add(flux, el, v);
-      } else {
-        atomicAdd(&flux[goff + el], v);
-      }
-    };
-    // Linear-mode contribution (rich walk callback).  The flux value is the
-    // plain path's expression; moments index = (flux index)*4 + vertex.
-    auto add_lin = [&](int32_t el, double t0, double t1, const WalkState &s) {
-      const double v = (t1 - t0) * s.seg_len * s.weight;
-      double m[4];
-      tet_moments(planes + (int64_t)el * 4, inv_h + (int64_t)el * 4, s, t0,
-                  t1, v, m);
-      if constexpr (Scored) {
-        const int64_t gsz = (int64_t)ngroups * nelems;
-        if (resp) {
-          for (int k = 0; k < nscores; ++k) {
-            const double r = resp[c * nscores + k];
-            const int64_t at = k * gsz + goff + el;
-            atomicAdd(&flux[at], v * r);
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-              atomicAdd(&moments[at * 4 + f], m[f] * r);
-          }
-          return;
-        }
-      } else if constexpr (Agg) {
-        wave_agg_atomic_add_linear(flux, moments, el, v, m);
-        return;
-      }
-      atomicAdd(&flux[goff + el], v);
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-        atomicAdd(&moments[(goff + el) * 4 + f], m[f]);
-    };
-    // Face-current contribution (face walk callback): the plain path's flux
-    // value and atomics, then the crossing's weight at (flux index)*4 +
-    // exit_face.  exit_face_in is -1 at the final-segment site, where the
-    // current code folds away after inlining.  An escaped particle leaving
-    // again where it sits is one departure (walk.h walk_current_face); the
-    // flag is read only by Currents instantiations.
+        Wave ? 0 : tally_group_offset(groups, c, ngroups, nelems);
+    // An escaped particle leaving again where it sits is one departure
+    // (walk.h walk_current_face); the flag is read only by Currents
+    // instantiations.
     bool reexit = false;
     if constexpr (Currents) reexit = escaped[i] != 0;
-    auto add_cur = [&](int32_t el, double t0, double t1, const WalkState &s,
-                       int exit_face_in) {
-      const int exit_face = walk_current_face<Periodic>(
-          reexit, nbr, el, exit_face_in, t1, reflective, face_bc, pidx);
-      const double v = (t1 - t0) * s.seg_len * s.weight;
-      if constexpr (Scored) {
-        const int64_t gsz = (int64_t)ngroups * nelems;
-        if (resp) {
-          for (int k = 0; k < nscores; ++k) {
-            const double r = resp[c * nscores + k];
-            const int64_t at = k * gsz + goff + el;
-            atomicAdd(&flux[at], v * r);
-            if (exit_face >= 0)
-              atomicAdd(&cur[at * 4 + exit_face], s.weight * r);
-          }
-          return;
-        }
-      } else if constexpr (Agg) {
-        wave_agg_atomic_add(flux, el, v);
-        if (exit_face >= 0) {
-          // keyed form: int32 key; the engine enables it only while
-          // nelems*4 fits
-          if (cur_keyed)
-            wave_agg_atomic_add(cur, el * 4 + exit_face, s.weight);
-          else
-            atomicAdd(&cur[(int64_t)el * 4 + exit_face], s.weight);
-        }
-        return;
-      }
-      atomicAdd(&flux[goff + el], v);
-      if (exit_face >= 0)
-        atomicAdd(&cur[(goff + el) * 4 + exit_face], s.weight);
-    };
+    TallySink<Mode, Scored, decltype(make_adder<Wave>(cur_keyed)),
+              /*ReexitRule=*/true, Periodic>
+        sink{make_adder<Wave>(cur_keyed), flux, Linear ? moments : cur, goff,
+             (int64_t)ngroups * nelems, resp, c, nscores, tmesh, reexit};
     auto walk = [&](auto &tally) {
       if constexpr (F32)
         walk_segment32<Periodic>(planes, planes32, nbr, e, o, d, weights[c],
@@ -513,12 +480,7 @@ __global__ void k_move(const Plane *__restrict__ planes,
                                tally, &out_elem, &out_pos, &out_esc,
                                reflective, face_bc, pidx, pelem, pshift);
     };
-    if constexpr (Linear)
-      walk(add_lin);
-    else if constexpr (Currents)
-      walk(add_cur);
-    else
-      walk(add);
+    walk(sink);
     if (out_elem == kWalkLost) {
       const unsigned long long k = atomicAdd(lost, 1ull);
       if (k < (unsigned long long)kMaxLostRecords) {
@@ -573,6 +535,8 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
   // block b to XCD b%8; giving each XCD one contiguous (spatially
   // compact, since callers keep lists near-Morton-ordered) index range
   // keeps its private L2 on one mesh region.
+  constexpr TallyMode Mode = kernel_tally_mode<Linear, Currents>;
+  const TallyMesh tmesh{planes, inv_h, nbr, face_bc, pidx, reflective};
   const unsigned bpx = gridDim.x / 8u;
   const unsigned vb = bpx ? (blockIdx.x % 8u) * bpx + blockIdx.x / 8u
                           : blockIdx.x;
@@ -585,63 +549,20 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
     int32_t oe;
     Vec3 op;
     bool esc;
-    const int64_t goff = groups ? (int64_t)(groups[i] % ngroups) * nelems : 0;
-    const int64_t gsz = (int64_t)ngroups * nelems;
-    auto add = [&](int32_t e, double v) {
-      if (resp) {
-        for (int k = 0; k < nscores; ++k)
-          atomicAdd(&flux[k * gsz + goff + e], v * resp[i * nscores + k]);
-      } else {
-        atomicAdd(&flux[goff + e], v);
-      }
-    };
+    // Plain atomics; responses are a run-time choice here.  Resumed walks
+    // need nothing extra for the moments (in_t only seeds t_cur), and a
+    // resumed walk starts inside its element, so the crossing its sender
+    // counted is not counted again -- there is no re-exit rule.
+    TallySink<Mode, /*Scored=*/true, AtomicAdder> sink{
+        AtomicAdder{}, flux, Linear ? moments : cur,
+        tally_group_offset(groups, i, ngroups, nelems),
+        (int64_t)ngroups * nelems, resp, i, nscores, tmesh, false};
     Vec3 od{d.x, d.y, d.z};
     const double rt = in_t ? in_t[i] : 0.0;
     const int32_t rp = in_prev ? in_prev[i] : -1;
     Vec3 oo{o.x, o.y, o.z};
     double ot = 0.0;
     int32_t opv = -1;
-    // Linear=true: flux plus the four moments (plain atomics; resumed
-    // walks need nothing extra, in_t only seeds t_cur).
-    auto add_lin = [&](int32_t e, double t0, double t1, const WalkState &s) {
-      const double v = (t1 - t0) * s.seg_len * s.weight;
-      double m[4];
-      tet_moments(planes + (int64_t)e * 4, inv_h + (int64_t)e * 4, s, t0, t1,
-                  v, m);
-      if (resp) {
-        for (int k = 0; k < nscores; ++k) {
-          const double r = resp[i * nscores + k];
-          const int64_t at = k * gsz + goff + e;
-          atomicAdd(&flux[at], v * r);
-#pragma unroll
-          for (int f = 0; f < 4; ++f) atomicAdd(&moments[at * 4 + f], m[f] * r);
-        }
-      } else {
-        atomicAdd(&flux[goff + e], v);
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-          atomicAdd(&moments[(goff + e) * 4 + f], m[f]);
-      }
-    };
-    // Currents=true: flux plus the crossing's weight on its exit face
-    // (plain atomics).  A resumed walk starts inside its element, so the
-    // crossing its sender counted is not counted again.
-    auto add_cur = [&](int32_t e, double t0, double t1, const WalkState &s,
-                       int exit_face) {
-      const double v = (t1 - t0) * s.seg_len * s.weight;
-      if (resp) {
-        for (int k = 0; k < nscores; ++k) {
-          const double r = resp[i * nscores + k];
-          const int64_t at = k * gsz + goff + e;
-          atomicAdd(&flux[at], v * r);
-          if (exit_face >= 0) atomicAdd(&cur[at * 4 + exit_face], s.weight * r);
-        }
-      } else {
-        atomicAdd(&flux[goff + e], v);
-        if (exit_face >= 0)
-          atomicAdd(&cur[(goff + e) * 4 + exit_face], s.weight);
-      }
-    };
     auto walk = [&](auto &tally) {
       if constexpr (F32)
         walk_segment32<true>(planes, planes32, nbr, elem[i], o, d, weights[i],
@@ -653,12 +574,7 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
                            tally, &oe, &op, &esc, reflective, face_bc, pidx,
                            pelem, pshift, &od, rt, rp, &oo, &ot, &opv);
     };
-    if constexpr (Linear)
-      walk(add_lin);
-    else if constexpr (Currents)
-      walk(add_cur);
-    else
-      walk(add);
+    walk(sink);
     int8_t st = 0;
     if (oe == kWalkLost) {
       st = 3;
@@ -1084,56 +1000,64 @@ public:
     PT_HIP_CHECK(hipSetDevice(device_));
     sync();
     const int64_t fsz = fsz_;
-    if (!d_bsum_) {
-      d_bsum_.allocate(fsz);
-      d_bsq_.allocate(fsz);
-      PT_HIP_CHECK(hipMemset(d_bsum_, 0, fsz * sizeof(double)));
-      PT_HIP_CHECK(hipMemset(d_bsq_, 0, fsz * sizeof(double)));
-    }
     if (slices_ > 1) {
       k_reduce_slices<<<grid_blocks(fsz), kBlock, 0, s_comp_>>>(d_flux_, fsz,
                                                                slices_);
       PT_HIP_CHECK(hipGetLastError());
     }
-    k_accumulate_batch<<<grid_blocks(fsz), kBlock, 0, s_comp_>>>(
-        d_flux_, d_bsum_, d_bsq_, fsz);
-    PT_HIP_CHECK(hipGetLastError());
-    if (linear) {
-      if (!d_msum_) {
-        d_msum_.allocate(fsz * 4);
-        PT_HIP_CHECK(hipMemset(d_msum_, 0, fsz * 4 * sizeof(double)));
-      }
-      k_accumulate_moments<<<grid_blocks(fsz * 4), kBlock, 0, s_comp_>>>(
-          d_moments_, d_msum_, fsz * 4);
-      PT_HIP_CHECK(hipGetLastError());
-    }
-    if (face_currents) {
-      if (!d_csum_) {
-        d_csum_.allocate(fsz * 4);
-        d_csq_.allocate(fsz * 4);
-        PT_HIP_CHECK(hipMemset(d_csum_, 0, fsz * 4 * sizeof(double)));
-        PT_HIP_CHECK(hipMemset(d_csq_, 0, fsz * 4 * sizeof(double)));
-      }
-      k_accumulate_batch<<<grid_blocks(fsz * 4), kBlock, 0, s_comp_>>>(
-          d_cur_, d_csum_, d_csq_, fsz * 4);
-      PT_HIP_CHECK(hipGetLastError());
-    }
+    close_batch(d_flux_, d_bsum_, &d_bsq_, fsz);
+    // there is no sum of squares for the moments
+    if (linear) close_batch(d_moments_, d_msum_, nullptr, fsz * 4);
+    if (face_currents) close_batch(d_cur_, d_csum_, &d_csq_, fsz * 4);
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
     nbatches_++;
   }
-  std::vector<double> batch_sum() const override { return fetch_acc(d_bsum_); }
-  std::vector<double> batch_sum_sq() const override { return fetch_acc(d_bsq_); }
+
+  // end_batch() for one tally array: add it into its running sum (and sum of
+  // squares, when it keeps one), then zero it.  The sums are allocated on
+  // first use.
+  void close_batch(double *tally, DeviceBuffer<double> &sum,
+                   DeviceBuffer<double> *sq, int64_t count) {
+    for (DeviceBuffer<double> *acc : {&sum, sq})
+      if (acc && !*acc) {
+        acc->allocate(count);
+        PT_HIP_CHECK(hipMemset(*acc, 0, count * sizeof(double)));
+      }
+    if (sq)
+      k_accumulate_batch<<<grid_blocks(count), kBlock, 0, s_comp_>>>(
+          tally, sum, *sq, count);
+    else
+      k_accumulate_moments<<<grid_blocks(count), kBlock, 0, s_comp_>>>(
+          tally, sum, count);
+    PT_HIP_CHECK(hipGetLastError());
+  }
+  std::vector<double> batch_sum() const override {
+    return fetch_tally(d_bsum_, fsz_);
+  }
+  std::vector<double> batch_sum_sq() const override {
+    return fetch_tally(d_bsq_, fsz_);
+  }
   int64_t num_batches() const override { return nbatches_; }
 
-  std::vector<double> fetch_acc(const double *p) const {
-    const int64_t fsz = fsz_;
-    std::vector<double> out(fsz, 0.0);
+  // Readback of an un-sliced tally array: the batch sums [fsz_], the
+  // moments, the currents and their batch sums [fsz_*4].  A null array (not
+  // allocated before the first end_batch) reads as zeros.
+  std::vector<double> fetch_tally(const double *p, int64_t count) const {
+    std::vector<double> out(count, 0.0);
     if (p) {
       sync();
-      PT_HIP_CHECK(hipMemcpy(out.data(), p, fsz * sizeof(double),
+      PT_HIP_CHECK(hipMemcpy(out.data(), p, count * sizeof(double),
                              hipMemcpyDeviceToHost));
     }
     return out;
+  }
+  // Upload of a whole [fsz_*4] array (moments or currents).
+  void set_tally4(double *dst, const double *src, int64_t n,
+                  const char *mismatch) {
+    if (n != fsz_ * 4) throw std::runtime_error(mismatch);
+    sync();
+    PT_HIP_CHECK(hipMemcpy(dst, src, n * sizeof(double),
+                           hipMemcpyHostToDevice));
   }
 
   std::vector<double> flux() const override {
@@ -1153,48 +1077,32 @@ public:
 
   std::vector<double> moments() const override {
     if (!linear) throw_not_linear();
-    return fetch_moments(d_moments_);
+    return fetch_tally(d_moments_, fsz_ * 4);
   }
   std::vector<double> moment_sum() const override {
     if (!linear) throw_not_linear();
-    return fetch_moments(d_msum_); // zeros before the first end_batch
-  }
-  std::vector<double> fetch_moments(const double *p) const {
-    std::vector<double> out(fsz_ * 4, 0.0);
-    if (p) {
-      sync();
-      PT_HIP_CHECK(hipMemcpy(out.data(), p, fsz_ * 4 * sizeof(double),
-                             hipMemcpyDeviceToHost));
-    }
-    return out;
+    return fetch_tally(d_msum_, fsz_ * 4);
   }
   void set_moments(const double *m, int64_t n) override {
     if (!linear) throw_not_linear();
-    if (n != fsz_ * 4) throw std::runtime_error("set_moments size mismatch");
-    sync();
-    PT_HIP_CHECK(hipMemcpy(d_moments_, m, n * sizeof(double),
-                           hipMemcpyHostToDevice));
+    set_tally4(d_moments_, m, n, "set_moments size mismatch");
   }
 
-  // Face currents share the moments' shape and readback.
   std::vector<double> currents() const override {
     if (!face_currents) throw_not_currents();
-    return fetch_moments(d_cur_);
+    return fetch_tally(d_cur_, fsz_ * 4);
   }
   std::vector<double> current_sum() const override {
     if (!face_currents) throw_not_currents();
-    return fetch_moments(d_csum_); // zeros before the first end_batch
+    return fetch_tally(d_csum_, fsz_ * 4);
   }
   std::vector<double> current_sum_sq() const override {
     if (!face_currents) throw_not_currents();
-    return fetch_moments(d_csq_);
+    return fetch_tally(d_csq_, fsz_ * 4);
   }
   void set_currents(const double *j, int64_t n) override {
     if (!face_currents) throw_not_currents();
-    if (n != fsz_ * 4) throw std::runtime_error("set_currents size mismatch");
-    sync();
-    PT_HIP_CHECK(hipMemcpy(d_cur_, j, n * sizeof(double),
-                           hipMemcpyHostToDevice));
+    set_tally4(d_cur_, j, n, "set_currents size mismatch");
   }
 
   std::vector<int32_t> elem_ids() const override {
@@ -1493,64 +1401,56 @@ private:
     PT_HIP_CHECK(hipGetLastError());
   }
 
-  template <bool F32, bool Scored, bool Periodic, bool Agg = false,
-            bool Linear = false, bool Currents = false>
-  void launch_move_one(const double *origin, const double *dest,
-                       const int8_t *flying, const double *weights,
-                       const uint16_t *groups, const double *resp,
-                       int64_t lo, int64_t hi, int steps) {
-    k_move<F32, Scored, Periodic, Agg, Linear, Currents>
-        <<<grid_blocks(hi - lo), kBlock, 0, s_comp_>>>(
-        d_planes_, d_planes32_, d_nbr_, grid_view_, d_s2c_, origin, dest,
-        flying, weights, groups, ngroups, d_pos_, d_elem_, d_escaped_,
-        d_flux_, d_lost_, d_lostrec_, d_loose_, lo, hi, loc_tol_, steps,
-        mesh_.nelems, slices_ - 1, reflective, d_face_bc_, resp, nscores,
-        d_pidx_, d_pelem_, d_pshift_, d_inv_h_, d_moments_, d_cur_,
-        cur_keyed_);
-    PT_HIP_CHECK(hipGetLastError());
+  // The k_move instantiation of a move.  Scored / periodic / wave-aggregated
+  // / linear / currents moves take dedicated instantiations; the plain
+  // (headline) one compiles without any of those features.  The tally arm
+  // is scored when responses are passed, else wave-aggregated when `agg`,
+  // else plain atomics; linear and face-current engines take their mode's
+  // instantiation of whichever arm and traversal the move would otherwise
+  // get.  All instantiations share one signature, so they fit one table.
+  using MoveKernel = decltype(&k_move<false>);
+  enum MoveArm { kArmPlain, kArmWave, kArmScored };
+  template <bool Linear, bool Currents>
+  static MoveKernel move_kernel(bool f32, bool per, MoveArm arm) {
+#define PT_MOVE_ARMS(F32, PER)                                               \
+  {                                                                          \
+    k_move<F32, false, PER, false, Linear, Currents>,                        \
+        k_move<F32, false, PER, true, Linear, Currents>,                     \
+        k_move<F32, true, PER, false, Linear, Currents>                      \
+  }
+    static constexpr MoveKernel table[2][2][3] = {
+        {PT_MOVE_ARMS(false, false), PT_MOVE_ARMS(false, true)},
+        {PT_MOVE_ARMS(true, false), PT_MOVE_ARMS(true, true)}};
+#undef PT_MOVE_ARMS
+    return table[f32][per][arm];
   }
 
   void launch_move_chunks(const double *origin, const double *dest,
                           const int8_t *flying, const double *weights,
                           const uint16_t *groups, const double *resp,
                           int64_t n, int steps) {
-    // Chunked launches: a ~2.6M-slot launch keeps each XCD's Morton-
-    // contiguous slot range's mesh working set inside its private L2.
-    // Scored / periodic / wave-aggregated / linear / currents moves take
-    // dedicated k_move instantiations; the plain (headline) instantiation
-    // compiles without any of those features.  Linear engines take the
-    // Linear twin, face-current engines the Currents twin, of whichever
-    // instantiation the move would otherwise get (the wave-aggregated one
-    // under the same `agg` condition).
-    const int64_t chunk = chunk_particles(n);
     const bool per = d_pidx_ != nullptr;
     // wave aggregation needs a single flat tally key per lane: plain
     // (unscored, ungrouped) moves only
     const bool agg = wave_agg() && !resp && !groups;
+    const MoveArm arm = resp ? kArmScored : (agg ? kArmWave : kArmPlain);
+    const MoveKernel kernel =
+        linear          ? move_kernel<true, false>(walk_fp32, per, arm)
+        : face_currents ? move_kernel<false, true>(walk_fp32, per, arm)
+                        : move_kernel<false, false>(walk_fp32, per, arm);
+    // Chunked launches: a ~2.6M-slot launch keeps each XCD's Morton-
+    // contiguous slot range's mesh working set inside its private L2.
+    const int64_t chunk = chunk_particles(n);
     for (int64_t lo = 0; lo < n; lo += chunk) {
       const int64_t hi = std::min(n, lo + chunk);
-      using T = std::true_type;
-      using F = std::false_type;
-      auto pick = [&](auto linc, auto curc) {
-        auto go = [&](auto f32c, auto scoredc, auto perc, auto aggc) {
-          launch_move_one<decltype(f32c)::value, decltype(scoredc)::value,
-                          decltype(perc)::value, decltype(aggc)::value,
-                          decltype(linc)::value, decltype(curc)::value>(
-              origin, dest, flying, weights, groups, resp, lo, hi, steps);
-        };
-        if (walk_fp32) {
-          if (resp)     per ? go(T{}, T{}, T{}, F{}) : go(T{}, T{}, F{}, F{});
-          else if (agg) per ? go(T{}, F{}, T{}, T{}) : go(T{}, F{}, F{}, T{});
-          else          per ? go(T{}, F{}, T{}, F{}) : go(T{}, F{}, F{}, F{});
-        } else {
-          if (resp)     per ? go(F{}, T{}, T{}, F{}) : go(F{}, T{}, F{}, F{});
-          else if (agg) per ? go(F{}, F{}, T{}, T{}) : go(F{}, F{}, F{}, T{});
-          else          per ? go(F{}, F{}, T{}, F{}) : go(F{}, F{}, F{}, F{});
-        }
-      };
-      if (linear)             pick(T{}, F{});
-      else if (face_currents) pick(F{}, T{});
-      else                    pick(F{}, F{});
+      kernel<<<grid_blocks(hi - lo), kBlock, 0, s_comp_>>>(
+          d_planes_, d_planes32_, d_nbr_, grid_view_, d_s2c_, origin, dest,
+          flying, weights, groups, ngroups, d_pos_, d_elem_, d_escaped_,
+          d_flux_, d_lost_, d_lostrec_, d_loose_, lo, hi, loc_tol_, steps,
+          mesh_.nelems, slices_ - 1, reflective, d_face_bc_, resp, nscores,
+          d_pidx_, d_pelem_, d_pshift_, d_inv_h_, d_moments_, d_cur_,
+          cur_keyed_);
+      PT_HIP_CHECK(hipGetLastError());
     }
   }
 

@@ -41,6 +41,7 @@ HEADERS = [
     "csrc/core/geom.h",
     "csrc/core/mesh.h",
     "csrc/core/walk.h",
+    "csrc/core/tally_sink.h",
     "csrc/core/engine.h",
     "csrc/core/origin_delta.h",
     "csrc/comm/comm.h",

@@ -7,6 +7,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 #include "../csrc/core/engine.h"
+#include "../csrc/core/tally_sink.h"
 #include "../cpp/partition_cpu_scenario.h"
 
 #include <cassert>
@@ -233,8 +234,76 @@ void threaded_currents_move() {
     if (x != 0.0) abort();
 }
 
+// The tally sink on its own (csrc/core/tally_sink.h): one crossing on a
+// two-tet mesh with ngroups=2, nscores=2, each mode with and without
+// responses; every written index and value against the literal formulas.
+template <TallyMode Mode> static void sink_case(bool with_resp) {
+  const int64_t nelems = 2;
+  const int G = 2, S = 2;
+  const int64_t fsz = nelems * G * S;
+  // the sink only evaluates these planes; they need not close up into tets
+  const Plane planes[8] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0},
+                           {-1, -1, -1, -1},
+                           {1, 1, 1, 1}, {-1, 0, 0, -1}, {0, -1, 0, -1},
+                           {0, 0, -1, -1}};
+  const double inv_h[8] = {1, 1, 1, 1, 0.5, 1, 1, 1};
+  const int32_t nbr[8] = {-1, -1, -1, 1, 0, -1, -1, -1};
+  const uint16_t groups[3] = {0, 0, 1};
+  const double resp[6] = {9, 9, 9, 9, 2, 3}; // particle 2: {2, 3}
+  const int64_t particle = 2;
+  const int32_t el = 1;
+  const int face = 2;
+  const double t0 = 0.25, t1 = 0.75;
+  WalkState s;
+  walk_init(s, el, Vec3{0.5, 0.5, 0.5}, Vec3{0.75, 1.0, 1.0}, 4.0);
+  std::vector<double> flux(fsz, 0.0), comp(fsz * 4, 0.0);
+  TallySink<Mode, true, PlainAdder<HostPlus>> sink{
+      {},
+      flux.data(),
+      comp.data(),
+      tally_group_offset(groups, particle, G, nelems),
+      (int64_t)G * nelems,
+      with_resp ? resp : nullptr,
+      particle,
+      S,
+      TallyMesh{planes, inv_h, nbr, nullptr, nullptr, false},
+      false};
+  sink(el, t0, t1, s, face);
+
+  const double v = (t1 - t0) * s.seg_len * s.weight;
+  double m[4] = {0, 0, 0, 0};
+  if (Mode == TallyMode::Linear)
+    tet_moments(planes + el * 4, inv_h + el * 4, s, t0, t1, v, m);
+  std::vector<double> want_flux(fsz, 0.0), want_comp(fsz * 4, 0.0);
+  for (int k = 0; k < (with_resp ? S : 1); ++k) {
+    const double r = with_resp ? resp[particle * S + k] : 1.0;
+    const int64_t at = k * (G * nelems) + 1 * nelems + el; // group 1
+    want_flux[at] = with_resp ? v * r : v;
+    if (Mode == TallyMode::Linear)
+      for (int f = 0; f < 4; ++f)
+        want_comp[at * 4 + f] = with_resp ? m[f] * r : m[f];
+    if (Mode == TallyMode::Currents)
+      want_comp[at * 4 + face] = with_resp ? s.weight * r : s.weight;
+  }
+  if (v <= 0.0 || flux != want_flux || comp != want_comp) abort();
+  // the final-segment site (exit_face -1) books flux but no current
+  if (Mode == TallyMode::Currents) {
+    sink(el, t1, 1.0, s, -1);
+    if (comp != want_comp || flux == want_flux) abort();
+  }
+}
+
+static void sink_cases() {
+  for (bool with_resp : {false, true}) {
+    sink_case<TallyMode::Flux>(with_resp);
+    sink_case<TallyMode::Linear>(with_resp);
+    sink_case<TallyMode::Currents>(with_resp);
+  }
+}
+
 int main() {
   golden();
+  sink_cases();
   fuzz();
   threaded_scored_move();
   threaded_linear_move();
