@@ -60,6 +60,11 @@ struct EngineStats {
   // Host time spent in the elision compare pass (seeding copies included),
   // cumulative seconds: what the feature costs the calling thread.
   double origin_pass_seconds = 0.0;
+  // Collision-estimator tallies (Engine::score_collisions / score_points):
+  // particles or points that scored, and those that did not because they
+  // are not in the mesh (unlocated or escaped).  Cumulative.
+  int64_t collisions_scored = 0;
+  int64_t collision_misses = 0;
 };
 
 // First-K lost-particle capture (walks that hit max_steps): enough to find
@@ -251,6 +256,85 @@ public:
     throw_not_currents();
   }
 
+  // Collision-estimator tallies -- only on engines created with
+  // collisions=true; every call below throws otherwise.  A second tally
+  // array laid out exactly like flux ([nscores x ngroups x nelems], flat
+  // index (k*ngroups + g)*nelems + e), filled ONLY by the explicit scoring
+  // calls below, never by move(): a point estimator (w/Sigma_t at each
+  // collision, scattering into a group, analog counts ...) needs no track
+  // and no geometry, just the element the engine already holds.  The scoring
+  // calls never modify `active`, particle state (position, element, escaped),
+  // flux, moments or currents; move() never touches the collisions.
+  // Combines freely with linear and with currents.
+  //
+  // score_collisions (n == num_particles): every particle i with
+  // active[i] != 0 whose held element e is >= 0 and which is not flagged
+  // escaped SCORES: with responses given, weights[i] * responses[i*nscores+k]
+  // is added to score k for every k; with responses == nullptr, weights[i]
+  // to score 0 only (move()'s rule); in group groups[i] % ngroups (group 0
+  // without groups), at element e.  Any other active particle is unlocated
+  // or escaped -- it sits on the vacuum face it left through, no longer in
+  // the mesh -- adds nothing and counts as a MISS.  A particle whose last
+  // walk was lost (hit max_steps) scores in the element the engine kept for
+  // it, the one the walk started from.
+  //
+  // score_points: n free points (any n, independent of num_particles;
+  // n == 0 is a no-op), xyz n*3 doubles.  Each is localized with the
+  // engine's grid and localization tolerance -- grid_locate on the device,
+  // Mesh::locate on the CPU, the calls and first-hit rule of
+  // copy_initial_position -- and a located point scores as above (its own
+  // weights / groups / responses row); a point outside the mesh is a miss.
+  // Loose hits count into loose_localizations.  Synchronous.
+  //
+  // EngineStats::collisions_scored / collision_misses count both calls.
+  // end_batch() adds the per-batch collisions into collision_sum and their
+  // squares into collision_sum_sq (a per-entry variance is meaningful, as for
+  // the currents) and zeroes them.
+  virtual void score_collisions(const int8_t *active, const double *weights,
+                                int64_t n, const uint16_t *groups = nullptr,
+                                const double *responses = nullptr) {
+    (void)active; (void)weights; (void)n; (void)groups; (void)responses;
+    throw_not_collisions();
+  }
+  virtual void score_points(int64_t n, const double *xyz,
+                            const double *weights,
+                            const uint16_t *groups = nullptr,
+                            const double *responses = nullptr) {
+    (void)n; (void)xyz; (void)weights; (void)groups; (void)responses;
+    throw_not_collisions();
+  }
+  // Device-resident twins, move_device's contract: every array already
+  // lives in this engine's device memory, nothing is staged, the kernel runs
+  // on the engine's compute stream.  Throw on the CPU engine.
+  virtual void score_collisions_device(const int8_t *d_active,
+                                       const double *d_weights, int64_t n,
+                                       const uint16_t *d_groups = nullptr,
+                                       const double *d_responses = nullptr) {
+    (void)d_active; (void)d_weights; (void)n; (void)d_groups;
+    (void)d_responses;
+    if (!collision_tallies) throw_not_collisions();
+    throw std::runtime_error("score_collisions_device requires the GPU engine");
+  }
+  virtual void score_points_device(int64_t n, const double *d_xyz,
+                                   const double *d_weights,
+                                   const uint16_t *d_groups = nullptr,
+                                   const double *d_responses = nullptr) {
+    (void)n; (void)d_xyz; (void)d_weights; (void)d_groups; (void)d_responses;
+    if (!collision_tallies) throw_not_collisions();
+    throw std::runtime_error("score_points_device requires the GPU engine");
+  }
+  virtual std::vector<double> collisions() const { throw_not_collisions(); }
+  virtual std::vector<double> collision_sum() const { throw_not_collisions(); }
+  virtual std::vector<double> collision_sum_sq() const {
+    throw_not_collisions();
+  }
+  // Overwrite the per-batch collisions (checkpoint restore); n must be the
+  // full flux size.
+  virtual void set_collisions(const double *c, int64_t n) {
+    (void)c; (void)n;
+    throw_not_collisions();
+  }
+
   // Restore particle state (checkpoint/resume support -- the reference has
   // none; a crash there loses the whole batch).
   virtual void set_particle_state(const double *pos, const int32_t *elem,
@@ -292,6 +376,11 @@ public:
   // accessor.)
   bool face_currents = false;
 
+  // Collision-estimator tallies enabled (see score_collisions()).  Fixed at
+  // construction (make_*_engine's trailing argument); read-only afterwards.
+  // (Named collision_tallies because collisions() is the accessor.)
+  bool collision_tallies = false;
+
   // fp32-traversal fast path (walk.h walk_advance32): candidate exit-face
   // decisions in fp32, crossings/tallies in fp64.  Controlled by
   // PUMITALLY_WALK=fp32|fp64; both engines honor it so CPU remains the
@@ -318,6 +407,10 @@ protected:
   [[noreturn]] static void throw_not_currents() {
     throw std::runtime_error(
         "face-current tallies are off: create the engine with currents=true");
+  }
+  [[noreturn]] static void throw_not_collisions() {
+    throw std::runtime_error(
+        "collision tallies are off: create the engine with collisions=true");
   }
 };
 
@@ -363,13 +456,15 @@ inline double loc_tol_rel() {
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
                                         int ngroups = 1, int nscores = 1,
                                         bool linear = false,
-                                        bool currents = false);
+                                        bool currents = false,
+                                        bool collisions = false);
 
 // Returns nullptr when no HIP device is available.
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
                                         int device, int ngroups = 1,
                                         int nscores = 1, bool linear = false,
-                                        bool currents = false);
+                                        bool currents = false,
+                                        bool collisions = false);
 
 // make_*_engine reject the one unsupported option pair up front.
 inline void check_tally_options(bool linear, bool currents) {

@@ -41,18 +41,21 @@ class CpuEngine final : public Engine {
   };
 
 public:
-  CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin, bool cur)
+  CpuEngine(Mesh mesh, int64_t n, int groups, int scores, bool lin, bool cur,
+            bool coll)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
     linear = lin;
     face_currents = cur;
+    collision_tallies = coll;
     flux_.assign(mesh_.nelems * ngroups * nscores, 0.0);
     if (linear) {
       mesh_.build_inv_heights();
       moments_.assign(flux_.size() * 4, 0.0);
     }
     if (face_currents) currents_.assign(flux_.size() * 4, 0.0);
+    if (collision_tallies) collisions_.assign(flux_.size(), 0.0);
     pos_.resize(n_ * 3);
     elem_.assign(n_, 0);
     escaped_.assign(n_, 0);
@@ -279,6 +282,45 @@ public:
     }
   }
 
+  // Collision-estimator scoring (engine.h).  One gather and one add per
+  // particle; a serial loop, so the sums are in caller order.
+  void score_collisions(const int8_t *active, const double *weights,
+                        int64_t n, const uint16_t *groups = nullptr,
+                        const double *responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    check_n(n);
+    for (int64_t i = 0; i < n; ++i)
+      if (active[i])
+        score_one(escaped_[i] ? -1 : elem_[i], weights, groups, responses, i);
+  }
+
+  void score_points(int64_t n, const double *xyz, const double *weights,
+                    const uint16_t *groups = nullptr,
+                    const double *responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    for (int64_t i = 0; i < n; ++i) {
+      bool loose = false;
+      const int32_t e = mesh_.locate(
+          Vec3{xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]}, loc_tol_, &loose);
+      if (loose) loose_++;
+      score_one(e, weights, groups, responses, i);
+    }
+  }
+
+  // Row i of the caller's arrays scores in element e, or misses (e < 0).
+  void score_one(int32_t e, const double *weights, const uint16_t *groups,
+                 const double *responses, int64_t i) {
+    if (e < 0) {
+      stats_.collision_misses++;
+      return;
+    }
+    score_contribute(PlainAdder<HostPlus>{}, collisions_.data(),
+                     tally_group_offset(groups, i, ngroups, mesh_.nelems),
+                     (int64_t)ngroups * mesh_.nelems, e, weights[i], responses,
+                     i, nscores);
+    stats_.collisions_scored++;
+  }
+
   void end_batch() override {
     if (batch_sum_.empty()) {
       batch_sum_.assign(flux_.size(), 0.0);
@@ -305,6 +347,17 @@ public:
         current_sum_[e] += currents_[e];
         current_sq_[e] += currents_[e] * currents_[e];
         currents_[e] = 0.0;
+      }
+    }
+    if (collision_tallies) {
+      if (collision_sum_.empty()) {
+        collision_sum_.assign(collisions_.size(), 0.0);
+        collision_sq_.assign(collisions_.size(), 0.0);
+      }
+      for (size_t e = 0; e < collisions_.size(); ++e) {
+        collision_sum_[e] += collisions_[e];
+        collision_sq_[e] += collisions_[e] * collisions_[e];
+        collisions_[e] = 0.0;
       }
     }
     nbatches_++;
@@ -372,6 +425,29 @@ public:
     if (n != (int64_t)currents_.size())
       throw std::runtime_error("set_currents size mismatch");
     std::memcpy(currents_.data(), j, n * sizeof(double));
+  }
+
+  std::vector<double> collisions() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return collisions_;
+  }
+  std::vector<double> collision_sum() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return collision_sum_.empty()
+               ? std::vector<double>(collisions_.size(), 0.0)
+               : collision_sum_;
+  }
+  std::vector<double> collision_sum_sq() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return collision_sq_.empty()
+               ? std::vector<double>(collisions_.size(), 0.0)
+               : collision_sq_;
+  }
+  void set_collisions(const double *c, int64_t n) override {
+    if (!collision_tallies) throw_not_collisions();
+    if (n != (int64_t)collisions_.size())
+      throw std::runtime_error("set_collisions size mismatch");
+    std::memcpy(collisions_.data(), c, n * sizeof(double));
   }
 
   void set_particle_state(const double *pos, const int32_t *elem,
@@ -495,6 +571,8 @@ private:
   std::vector<double> moments_, moment_sum_; // linear mode only, else empty
   // face currents only, else empty
   std::vector<double> currents_, current_sum_, current_sq_;
+  // collision tallies only, else empty; never a for_each_particle target
+  std::vector<double> collisions_, collision_sum_, collision_sq_;
   int64_t nbatches_ = 0;
   std::vector<int32_t> elem_;
   std::vector<uint8_t> escaped_;
@@ -509,10 +587,11 @@ private:
 
 std::unique_ptr<Engine> make_cpu_engine(Mesh mesh, int64_t num_particles,
                                         int ngroups, int nscores,
-                                        bool linear, bool currents) {
+                                        bool linear, bool currents,
+                                        bool collisions) {
   check_tally_options(linear, currents);
   return std::make_unique<CpuEngine>(std::move(mesh), num_particles, ngroups,
-                                     nscores, linear, currents);
+                                     nscores, linear, currents, collisions);
 }
 
 } // namespace pumitally

@@ -10,7 +10,7 @@
 namespace pumitally {
 
 std::unique_ptr<Engine> make_gpu_engine(Mesh, int64_t, int, int, int, bool linear,
-                                        bool currents) {
+                                        bool currents, bool) {
   check_tally_options(linear, currents);
   return nullptr;
 }

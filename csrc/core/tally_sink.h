@@ -48,6 +48,27 @@ PT_HD int64_t tally_group_offset(const uint16_t *__restrict__ groups,
   return groups ? (int64_t)(groups[particle] % ngroups) * nelems : 0;
 }
 
+// A point score (Engine::score_collisions / score_points): what one scoring
+// particle or free point, sitting in element `el` with weight `w`, adds to
+// the flux-shaped `array`.  No track and no mesh data enter.  Scores and
+// groups apply as in the walk sink: with `resp`, score k gets
+// w * resp[particle*nscores + k] at k*gsz + goff + el; without, score 0 alone
+// gets w.  `goff` is tally_group_offset of the particle, `gsz` the score
+// stride ngroups*nelems.  Values go through Adder::flux, so any adder of the
+// walk sink serves.
+template <class Adder>
+PT_HD void score_contribute(const Adder &add, double *array, int64_t goff,
+                            int64_t gsz, int32_t el, double w,
+                            const double *__restrict__ resp, int64_t particle,
+                            int nscores) {
+  if (resp) {
+    for (int k = 0; k < nscores; ++k)
+      add.flux(array, k * gsz + goff + el, w * resp[particle * nscores + k]);
+    return;
+  }
+  add.flux(array, goff + el, w);
+}
+
 // The mesh arrays the Linear and Currents modes read; Flux reads none.
 struct TallyMesh {
   const Plane *planes;     // Linear

@@ -362,6 +362,129 @@ inline bool wave_agg() {
   return v;
 }
 
+// Collision scoring under run aggregation: PUMITALLY_WAVE_AGG as for the
+// walk, but read per engine, at construction, so one process can time both
+// arms (benchmarks/collision_cost.py).  Default on: measured on MI355X at
+// 10M particles, 0.220 ms aggregated against 0.337 ms plain per step for a
+// spread source, 3.53 against 93.0 ms for the 2 % point source
+// (profiles/README.md).
+inline bool collisions_run_agg() {
+  const char *s = getenv("PUMITALLY_WAVE_AGG");
+  return s ? atoi(s) != 0 : true;
+}
+
+// What a wave's lanes did in one pass of a scoring loop, counted once per
+// wave: every lane of the wave executes this (the loops below keep their
+// trip count wave-uniform), so the two popcounts are the same value in all
+// of them and each lane's running totals are the wave's.
+__device__ __forceinline__ void score_count(bool active, bool hit,
+                                            unsigned long long &scored,
+                                            unsigned long long &missed) {
+  const unsigned long long am = __ballot(active), hm = __ballot(hit);
+  scored += (unsigned long long)__popcll(hm);
+  missed += (unsigned long long)__popcll(am & ~hm);
+}
+
+__device__ __forceinline__ void
+score_count_flush(unsigned long long scored, unsigned long long missed,
+                  unsigned long long *__restrict__ counts) {
+  if ((threadIdx.x & 63u) == 0) {
+    if (scored) atomicAdd(&counts[0], scored);
+    if (missed) atomicAdd(&counts[1], missed);
+  }
+}
+
+// Engine::score_collisions on the device: one gather and one add per active
+// particle, no geometry.  Iterates particle SLOTS (Morton order) with
+// k_move's XCD-aware block->range mapping, so a wave's 64 lanes are
+// neighbouring slots -- hence mostly the same few elements; the caller's
+// arrays are gathered through s2c.  Reads elem/escaped, writes neither.
+// Wave=true (host: no groups, no responses) keys the add on the int32
+// element id and issues one atomicAdd per run of equal elements
+// (wave_run_sum); Wave=false adds every value with a plain atomicAdd.
+// counts[0] += particles that scored, counts[1] += misses.
+template <bool Wave>
+__global__ void k_score_slots(const int32_t *__restrict__ s2c,
+                              const int32_t *__restrict__ elem,
+                              const uint8_t *__restrict__ escaped,
+                              const int8_t *__restrict__ active,
+                              const double *__restrict__ weights,
+                              const uint16_t *__restrict__ groups,
+                              const double *__restrict__ resp, int ngroups,
+                              int nscores, int64_t nelems,
+                              double *__restrict__ coll,
+                              unsigned long long *__restrict__ counts,
+                              int64_t n) {
+  const unsigned bpx = gridDim.x / 8u;
+  const unsigned vb = bpx ? (blockIdx.x % 8u) * bpx + blockIdx.x / 8u
+                          : blockIdx.x;
+  const int64_t per_blk = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t base = (int64_t)vb * per_blk;
+  const int64_t end = base + per_blk < n ? base + per_blk : n;
+  const int lane = (int)(threadIdx.x & 63u);
+  unsigned long long scored = 0, missed = 0;
+  // i0 is the wave's first slot of the pass: the same in all 64 lanes
+  for (int64_t i0 = base + (threadIdx.x - lane); i0 < end; i0 += blockDim.x) {
+    const int64_t i = i0 + lane;
+    int64_t c = 0;
+    int32_t e = -1;
+    bool act = false;
+    if (i < end) {
+      c = s2c[i];
+      act = active[c] != 0;
+    }
+    if (act && !escaped[i]) e = elem[i];
+    score_count(act, e >= 0, scored, missed);
+    if (e < 0) continue;
+    const int64_t goff =
+        Wave ? 0 : tally_group_offset(groups, c, ngroups, nelems);
+    score_contribute(make_adder<Wave>(false), coll, goff,
+                     (int64_t)ngroups * nelems, e, weights[c],
+                     Wave ? nullptr : resp, c, nscores);
+  }
+  score_count_flush(scored, missed, counts);
+}
+
+// Engine::score_points on the device: n free points in caller order,
+// grid-stride, each localized with grid_locate (copy_initial_position's
+// call) and scored like a particle.  Runs of equal elements only form when
+// the caller sorted the points; the result does not depend on it.
+template <bool Wave>
+__global__ void k_score_points(const Plane *__restrict__ planes, GridView grid,
+                               const double *__restrict__ xyz,
+                               const double *__restrict__ weights,
+                               const uint16_t *__restrict__ groups,
+                               const double *__restrict__ resp, int ngroups,
+                               int nscores, int64_t nelems, double tol,
+                               double *__restrict__ coll,
+                               unsigned long long *__restrict__ counts,
+                               unsigned long long *__restrict__ loose,
+                               int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  unsigned long long scored = 0, missed = 0;
+  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane);
+       i0 < n; i0 += stride) {
+    const int64_t i = i0 + lane;
+    int32_t e = -1;
+    if (i < n) {
+      bool used_loose = false;
+      e = grid_locate(grid, planes,
+                      Vec3{xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]}, tol,
+                      &used_loose);
+      if (used_loose) atomicAdd(loose, 1ull); // rare by construction
+    }
+    score_count(i < n, e >= 0, scored, missed);
+    if (e < 0) continue;
+    const int64_t goff =
+        Wave ? 0 : tally_group_offset(groups, i, ngroups, nelems);
+    score_contribute(make_adder<Wave>(false), coll, goff,
+                     (int64_t)ngroups * nelems, e, weights[i],
+                     Wave ? nullptr : resp, i, nscores);
+  }
+  score_count_flush(scored, missed, counts);
+}
+
 // The fused move kernel: phase A (relocation of flying, non-escaped
 // particles whose origin changed) + phase B (tallied walk to destination).
 //
@@ -674,18 +797,24 @@ int grid_blocks(int64_t work) {
 class GpuEngine final : public Engine {
 public:
   GpuEngine(Mesh mesh, int64_t n, int device, int groups, int scores,
-            bool lin, bool cur)
+            bool lin, bool cur, bool coll)
       : mesh_(std::move(mesh)), n_(n) {
     ngroups = groups < 1 ? 1 : groups;
     nscores = scores < 1 ? 1 : scores;
     linear = lin;
     face_currents = cur;
+    collision_tallies = coll;
     PT_HIP_CHECK(hipSetDevice(device));
     device_ = device;
     s_copy_.create();
     s_comp_.create();
     for (auto &ev : copy_ev_) ev.create();
     for (auto &ev : kernels_done_) ev.create();
+    if (collision_tallies) {
+      s_score_.create();
+      score_copied_.create();
+      score_done_.create();
+    }
 
     // Mesh upload (once).
     d_planes_ = upload(mesh_.planes);
@@ -729,6 +858,14 @@ public:
       PT_HIP_CHECK(hipMemset(d_cur_, 0, fsz_ * 4 * sizeof(double)));
       // the keyed aggregation carries el*4+f in an int32 lane value
       cur_keyed_ = currents_keyed_agg() && mesh_.nelems < ((int64_t)1 << 29);
+    }
+    if (collision_tallies) {
+      d_coll_.allocate(fsz_);
+      PT_HIP_CHECK(hipMemset(d_coll_, 0, fsz_ * sizeof(double)));
+      d_coll_counts_.allocate(2);
+      PT_HIP_CHECK(
+          hipMemset(d_coll_counts_, 0, 2 * sizeof(unsigned long long)));
+      coll_agg_ = collisions_run_agg();
     }
     PT_HIP_CHECK(hipMemset(d_lost_, 0, sizeof(unsigned long long)));
     PT_HIP_CHECK(hipMemset(d_loose_, 0, sizeof(unsigned long long)));
@@ -880,6 +1017,119 @@ public:
     stats_.moves++;
   }
 
+  // ---- collision-estimator scoring (engine.h) ---------------------------
+  //
+  // score_collisions stages the caller's arrays into buffers of its own
+  // (sc_*, allocated on first use: 11 + 8*nscores B per particle with groups
+  // and responses) on a stream of its own, so it neither uses nor advances
+  // anything move() owns: not the parity buffers d_*_[p], not parity_, not
+  // the elision shadow, not moves_since_sort_.  Ordering:
+  //   * uploads (s_score_) wait for score_done_, the previous score kernel,
+  //     the only other reader or writer of sc_*;
+  //   * the kernel goes on s_comp_ after score_copied_, i.e. behind every
+  //     queued move and re-sort, and sees the state they leave;
+  //   * the call returns once s_score_ has drained, i.e. the copies have
+  //     consumed the caller's arrays (move()'s contract); the kernel keeps
+  //     running async, and every readback syncs s_comp_.
+  void score_collisions(const int8_t *active, const double *weights,
+                        int64_t n, const uint16_t *groups = nullptr,
+                        const double *responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    check_n(n);
+    if (n == 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    if (!sc_active_) {
+      sc_active_.allocate(n_);
+      sc_weights_.allocate(n_);
+    }
+    if (groups && !sc_groups_) sc_groups_.allocate(n_);
+    if (responses && !sc_resp_) sc_resp_.allocate(n_ * nscores);
+    if (score_queued_)
+      PT_HIP_CHECK(hipStreamWaitEvent(s_score_, score_done_, 0));
+    stage(active, n * sizeof(int8_t), sc_active_, s_score_);
+    stage(weights, n * sizeof(double), sc_weights_, s_score_);
+    if (groups) stage(groups, n * sizeof(uint16_t), sc_groups_, s_score_);
+    if (responses)
+      stage(responses, n * nscores * sizeof(double), sc_resp_, s_score_);
+    PT_HIP_CHECK(hipEventRecord(score_copied_, s_score_));
+    PT_HIP_CHECK(hipStreamWaitEvent(s_comp_, score_copied_, 0));
+    launch_score_slots(sc_active_, sc_weights_, groups ? sc_groups_ : nullptr,
+                       responses ? sc_resp_ : nullptr);
+    PT_HIP_CHECK(hipEventRecord(score_done_, s_comp_));
+    score_queued_ = true;
+    PT_HIP_CHECK(hipStreamSynchronize(s_score_));
+  }
+
+  void score_collisions_device(const int8_t *d_active, const double *d_weights,
+                               int64_t n, const uint16_t *d_groups = nullptr,
+                               const double *d_responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    check_n(n);
+    if (n == 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    launch_score_slots(d_active, d_weights, d_groups, d_responses);
+  }
+
+  void launch_score_slots(const int8_t *active, const double *weights,
+                          const uint16_t *groups, const double *resp) {
+    const auto kernel = coll_agg_ && !groups && !resp ? k_score_slots<true>
+                                                      : k_score_slots<false>;
+    kernel<<<grid_blocks(n_), kBlock, 0, s_comp_>>>(
+        d_s2c_, d_elem_, d_escaped_, active, weights, groups, resp, ngroups,
+        nscores, mesh_.nelems, d_coll_, d_coll_counts_, n_);
+    PT_HIP_CHECK(hipGetLastError());
+  }
+
+  // Grow-once scratch of score_points, like WalkRawScratch.
+  struct ScorePointsScratch {
+    DeviceBuffer<double> xyz, w, resp;
+    DeviceBuffer<uint16_t> groups;
+  };
+
+  void score_points(int64_t n, const double *xyz, const double *weights,
+                    const uint16_t *groups = nullptr,
+                    const double *responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    if (n <= 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    // the previous call synchronized s_comp_ before returning, so the
+    // scratch is free for reuse here
+    sp_.xyz.reserve(n * 3);
+    sp_.w.reserve(n);
+    if (groups) sp_.groups.reserve(n);
+    if (responses) sp_.resp.reserve(n * nscores);
+    PT_HIP_CHECK(hipMemcpy(sp_.xyz, xyz, n * 3 * 8, hipMemcpyHostToDevice));
+    PT_HIP_CHECK(hipMemcpy(sp_.w, weights, n * 8, hipMemcpyHostToDevice));
+    if (groups)
+      PT_HIP_CHECK(hipMemcpy(sp_.groups, groups, n * 2, hipMemcpyHostToDevice));
+    if (responses)
+      PT_HIP_CHECK(hipMemcpy(sp_.resp, responses, n * nscores * 8,
+                             hipMemcpyHostToDevice));
+    launch_score_points(n, sp_.xyz, sp_.w, groups ? sp_.groups.get() : nullptr,
+                        responses ? sp_.resp.get() : nullptr);
+    PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
+  }
+
+  void score_points_device(int64_t n, const double *d_xyz,
+                           const double *d_weights,
+                           const uint16_t *d_groups = nullptr,
+                           const double *d_responses = nullptr) override {
+    if (!collision_tallies) throw_not_collisions();
+    if (n <= 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    launch_score_points(n, d_xyz, d_weights, d_groups, d_responses);
+  }
+
+  void launch_score_points(int64_t n, const double *xyz, const double *weights,
+                           const uint16_t *groups, const double *resp) {
+    const auto kernel = coll_agg_ && !groups && !resp ? k_score_points<true>
+                                                      : k_score_points<false>;
+    kernel<<<grid_blocks(n), kBlock, 0, s_comp_>>>(
+        d_planes_, grid_view_, xyz, weights, groups, resp, ngroups, nscores,
+        mesh_.nelems, loc_tol_, d_coll_, d_coll_counts_, d_loose_, n);
+    PT_HIP_CHECK(hipGetLastError());
+  }
+
   // Persistent scratch for walk_raw.  The partitioned driver calls
   // walk_raw once per exchange round; per-call hipMalloc/hipFree pairs
   // would device-sync every round, so the buffers are grown once and
@@ -1009,6 +1259,7 @@ public:
     // there is no sum of squares for the moments
     if (linear) close_batch(d_moments_, d_msum_, nullptr, fsz * 4);
     if (face_currents) close_batch(d_cur_, d_csum_, &d_csq_, fsz * 4);
+    if (collision_tallies) close_batch(d_coll_, d_collsum_, &d_collsq_, fsz);
     PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
     nbatches_++;
   }
@@ -1105,6 +1356,26 @@ public:
     set_tally4(d_cur_, j, n, "set_currents size mismatch");
   }
 
+  std::vector<double> collisions() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return fetch_tally(d_coll_, fsz_);
+  }
+  std::vector<double> collision_sum() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return fetch_tally(d_collsum_, fsz_);
+  }
+  std::vector<double> collision_sum_sq() const override {
+    if (!collision_tallies) throw_not_collisions();
+    return fetch_tally(d_collsq_, fsz_);
+  }
+  void set_collisions(const double *c, int64_t n) override {
+    if (!collision_tallies) throw_not_collisions();
+    if (n != fsz_) throw std::runtime_error("set_collisions size mismatch");
+    sync();
+    PT_HIP_CHECK(hipMemcpy(d_coll_, c, n * sizeof(double),
+                           hipMemcpyHostToDevice));
+  }
+
   std::vector<int32_t> elem_ids() const override {
     auto [s2c, elem] = fetch<int32_t>(d_elem_, 1);
     std::vector<int32_t> out(n_);
@@ -1133,6 +1404,13 @@ public:
         hipMemcpy(&loose, d_loose_, sizeof loose, hipMemcpyDeviceToHost));
     stats_.lost_particles = (int64_t)lost;
     stats_.loose_localizations = (int64_t)loose;
+    if (collision_tallies) {
+      unsigned long long c[2] = {0, 0};
+      PT_HIP_CHECK(
+          hipMemcpy(c, d_coll_counts_, sizeof c, hipMemcpyDeviceToHost));
+      stats_.collisions_scored = (int64_t)c[0];
+      stats_.collision_misses = (int64_t)c[1];
+    }
     return stats_;
   }
 
@@ -1522,6 +1800,10 @@ private:
   Stream s_copy_, s_comp_;
   std::array<Event, 2> copy_ev_;
   std::array<Event, 2> kernels_done_;
+  // collision tallies only: score_collisions' upload stream and its fences
+  Stream s_score_;
+  Event score_copied_, score_done_;
+  bool score_queued_ = false;
 
   PinnedBuffer<int32_t> h_patch_idx_;
   PinnedBuffer<double> h_patch_xyz_;
@@ -1551,6 +1833,17 @@ private:
   // and their end_batch sum / sum of squares (allocated on first use).
   DeviceBuffer<double> d_cur_, d_csum_, d_csq_;
   bool cur_keyed_ = false;
+  // Collision tallies only (null otherwise): the un-sliced collisions
+  // [fsz_], their end_batch sum / sum of squares (allocated on first use),
+  // the {scored, missed} counters, score_collisions' staging buffers and
+  // score_points' scratch (both allocated on first use).
+  DeviceBuffer<double> d_coll_, d_collsum_, d_collsq_;
+  DeviceBuffer<unsigned long long> d_coll_counts_;
+  bool coll_agg_ = true;
+  DeviceBuffer<int8_t> sc_active_;
+  DeviceBuffer<double> sc_weights_, sc_resp_;
+  DeviceBuffer<uint16_t> sc_groups_;
+  ScorePointsScratch sp_;
   DeviceBuffer<uint32_t> d_face_bc_;
   DeviceBuffer<int32_t> d_pidx_, d_pelem_;
   DeviceBuffer<double> d_pshift_;
@@ -1573,7 +1866,8 @@ private:
 
 std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
                                         int device, int ngroups, int nscores,
-                                        bool linear, bool currents) {
+                                        bool linear, bool currents,
+                                        bool collisions) {
   check_tally_options(linear, currents);
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= device) {
@@ -1581,7 +1875,8 @@ std::unique_ptr<Engine> make_gpu_engine(Mesh mesh, int64_t num_particles,
     return nullptr;
   }
   return std::make_unique<GpuEngine>(std::move(mesh), num_particles, device,
-                                     ngroups, nscores, linear, currents);
+                                     ngroups, nscores, linear, currents,
+                                     collisions);
 }
 
 } // namespace pumitally

@@ -46,9 +46,10 @@ struct PyEngine {
 
   PyEngine(const Mesh &mesh, int64_t n, const std::string &device,
            int ngroups = 1, int nscores = 1, bool linear = false,
-           bool currents = false) {
+           bool currents = false, bool collisions = false) {
     if (device == "cpu") {
-      eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents);
+      eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents,
+                            collisions);
     } else {
       int ordinal = 0;
       if (device.rfind("cuda:", 0) == 0) ordinal = std::stoi(device.substr(5));
@@ -56,11 +57,12 @@ struct PyEngine {
       else if (device != "cuda" && device != "gpu" && device != "auto")
         throw std::runtime_error("device must be cpu/cuda[:N]/auto");
       eng = make_gpu_engine(mesh, n, ordinal, ngroups, nscores, linear,
-                            currents);
+                            currents, collisions);
       if (eng) {
         gpu = true;
       } else if (device == "auto") {
-        eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents);
+        eng = make_cpu_engine(mesh, n, ngroups, nscores, linear, currents,
+                              collisions);
       } else {
         // Fail loudly: a GPU was requested but none is usable.  GPU tests
         // must never fall back silently to the CPU oracle.
@@ -69,6 +71,32 @@ struct PyEngine {
     }
   }
 };
+
+// The optional groups / responses arguments of the scoring calls: null for
+// None, else the array's data after a size check (`what` names the call).
+using GroupsArray =
+    py::array_t<uint16_t, py::array::c_style | py::array::forcecast>;
+using DoubleArray =
+    py::array_t<double, py::array::c_style | py::array::forcecast>;
+
+const uint16_t *optional_groups(py::object obj, GroupsArray &keep, int64_t n,
+                                const char *what) {
+  if (obj.is_none()) return nullptr;
+  keep = obj.cast<GroupsArray>();
+  if ((int64_t)keep.size() != n)
+    throw std::runtime_error(std::string(what) + ": groups size mismatch");
+  return keep.data();
+}
+
+const double *optional_responses(py::object obj, DoubleArray &keep, int64_t n,
+                                 int nscores, const char *what) {
+  if (obj.is_none()) return nullptr;
+  keep = obj.cast<DoubleArray>();
+  if ((int64_t)keep.size() != n * nscores)
+    throw std::runtime_error(std::string(what) +
+                             ": responses size must be n*nscores");
+  return keep.data();
+}
 
 // Pinned host allocation exposed as a numpy array (zero-copy H2D staging for
 // the bench / host transport codes).  Falls back to pageable memory when no
@@ -710,10 +738,14 @@ PYBIND11_MODULE(_core, m) {
 
   py::class_<PyEngine>(m, "Engine")
       .def(py::init<const Mesh &, int64_t, const std::string &, int, int,
-                    bool, bool>(),
+                    bool, bool, bool>(),
            py::arg("mesh"), py::arg("num_particles"), py::arg("device") = "auto",
            py::arg("ngroups") = 1, py::arg("nscores") = 1,
-           py::arg("linear") = false, py::arg("currents") = false)
+           py::arg("linear") = false, py::arg("currents") = false,
+           py::arg("collisions") = false)
+      .def_property_readonly(
+          "collision_tallies",
+          [](const PyEngine &e) { return e.eng->collision_tallies; })
       .def_property_readonly("linear",
                              [](const PyEngine &e) { return e.eng->linear; })
       .def_property_readonly(
@@ -984,6 +1016,77 @@ PYBIND11_MODULE(_core, m) {
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> j) {
              e.eng->set_currents(j.data(), (int64_t)j.size());
            })
+      // collision-estimator tallies (engine.h); every call below throws
+      // RuntimeError on an engine built without collisions=True.  The host
+      // calls take exact dtypes (no silent conversion of active / weights),
+      // like move().
+      .def("score_collisions",
+           [](PyEngine &e, py::array_t<int8_t, py::array::c_style> active,
+              py::array_t<double, py::array::c_style> weights,
+              py::object groups, py::object responses) {
+             const int64_t n = e.eng->num_particles();
+             if ((int64_t)active.size() != n || (int64_t)weights.size() != n)
+               throw std::runtime_error("score_collisions: array size mismatch");
+             GroupsArray garr;
+             DoubleArray rarr;
+             const uint16_t *gp =
+                 optional_groups(groups, garr, n, "score_collisions");
+             const double *rp = optional_responses(
+                 responses, rarr, n, e.eng->nscores, "score_collisions");
+             py::gil_scoped_release nogil;
+             e.eng->score_collisions(active.data(), weights.data(), n, gp, rp);
+           },
+           py::arg("active"), py::arg("weights"),
+           py::arg("groups") = py::none(), py::arg("responses") = py::none())
+      .def("score_points",
+           [](PyEngine &e, py::array_t<double, py::array::c_style> points,
+              py::array_t<double, py::array::c_style> weights,
+              py::object groups, py::object responses) {
+             const int64_t n = (int64_t)weights.size();
+             if ((int64_t)points.size() != n * 3)
+               throw std::runtime_error("score_points: points must have size 3*n");
+             GroupsArray garr;
+             DoubleArray rarr;
+             const uint16_t *gp =
+                 optional_groups(groups, garr, n, "score_points");
+             const double *rp = optional_responses(
+                 responses, rarr, n, e.eng->nscores, "score_points");
+             py::gil_scoped_release nogil;
+             e.eng->score_points(n, points.data(), weights.data(), gp, rp);
+           },
+           py::arg("points"), py::arg("weights"),
+           py::arg("groups") = py::none(), py::arg("responses") = py::none())
+      // raw device-pointer twins (integers, as for move_device); the Python
+      // wrapper validates device/dtype/shape
+      .def("score_collisions_device",
+           [](PyEngine &e, uintptr_t active_ptr, uintptr_t weights_ptr,
+              uintptr_t groups_ptr, uintptr_t responses_ptr) {
+             py::gil_scoped_release nogil;
+             e.eng->score_collisions_device(
+                 (const int8_t *)active_ptr, (const double *)weights_ptr,
+                 e.eng->num_particles(), (const uint16_t *)groups_ptr,
+                 (const double *)responses_ptr);
+           },
+           py::arg("active_ptr"), py::arg("weights_ptr"),
+           py::arg("groups_ptr") = 0, py::arg("responses_ptr") = 0)
+      .def("score_points_device",
+           [](PyEngine &e, int64_t n, uintptr_t points_ptr,
+              uintptr_t weights_ptr, uintptr_t groups_ptr,
+              uintptr_t responses_ptr) {
+             py::gil_scoped_release nogil;
+             e.eng->score_points_device(
+                 n, (const double *)points_ptr, (const double *)weights_ptr,
+                 (const uint16_t *)groups_ptr, (const double *)responses_ptr);
+           },
+           py::arg("n"), py::arg("points_ptr"), py::arg("weights_ptr"),
+           py::arg("groups_ptr") = 0, py::arg("responses_ptr") = 0)
+      .def("collisions", [](const PyEngine &e) { return vec_to_np(e.eng->collisions()); })
+      .def("collision_sum", [](const PyEngine &e) { return vec_to_np(e.eng->collision_sum()); })
+      .def("collision_sum_sq", [](const PyEngine &e) { return vec_to_np(e.eng->collision_sum_sq()); })
+      .def("set_collisions",
+           [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> c) {
+             e.eng->set_collisions(c.data(), (int64_t)c.size());
+           })
       .def("set_particle_state",
            [](PyEngine &e, py::array_t<double, py::array::c_style | py::array::forcecast> pos,
               py::array_t<int32_t, py::array::c_style | py::array::forcecast> elem,
@@ -1009,6 +1112,8 @@ PYBIND11_MODULE(_core, m) {
         d["origins_elided"] = s.origins_elided;
         d["origin_bytes_uploaded"] = s.origin_bytes_uploaded;
         d["origin_pass_seconds"] = s.origin_pass_seconds;
+        d["collisions_scored"] = s.collisions_scored;
+        d["collision_misses"] = s.collision_misses;
         return d;
       })
       // First-K lost-walk capture: (k, 4) array of

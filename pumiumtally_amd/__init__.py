@@ -61,6 +61,45 @@ normalize_flux = _core.normalize_flux
 write_tally_vtk = _core.write_tally_vtk
 
 
+def _device_ptr(t, dtype, numel, who):
+    """Device address of t (0 for None) after checking that it exposes
+    __cuda_array_interface__ with exactly `dtype` x `numel`, C-contiguous.
+    `who` names the calling method in the error messages."""
+    if t is None:
+        return 0
+    iface = getattr(t, "__cuda_array_interface__", None)
+    if iface is None:
+        raise TypeError(f"{who} expects CUDA tensors/arrays")
+    import math
+    n = math.prod(iface["shape"]) if iface["shape"] else 1
+    if iface["typestr"] != dtype or n != numel:
+        raise TypeError(
+            f"expected {dtype} x{numel}, got {iface['typestr']} x{n}")
+    strides = iface.get("strides")
+    if strides is not None:
+        # C-contiguity required (None == C-contiguous per protocol)
+        itemsize = int(dtype[-1])
+        expect = []
+        acc = itemsize
+        for s in reversed(iface["shape"]):
+            expect.append(acc)
+            acc *= s
+        if list(strides) != list(reversed(expect)):
+            raise TypeError(f"{who} requires contiguous tensors")
+    return iface["data"][0]
+
+
+def _sync_torch():
+    """Order against torch's stream: tensors produced by torch ops
+    (.to(device), fills) must be materialized before an engine kernel,
+    which runs on the engine's own HIP stream."""
+    import sys
+    if "torch" in sys.modules:
+        torch = sys.modules["torch"]
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+
+
 class TallyEngine:
     """Track-length tally engine over a tet mesh.
 
@@ -78,22 +117,32 @@ class TallyEngine:
     face), from which net_current() and leakage() follow; flux() is
     unchanged by it.  Off by default; fixed at construction
     (face_currents tells); not available together with linear=True.
+
+    collisions=True adds a second, flux-shaped tally filled only by the
+    explicit scoring calls score_collisions() / score_points() (and their
+    *_from_device twins), never by move(): the collision estimator, scored
+    at particle positions with no track and no geometry (collisions()).
+    flux(), moments() and currents() are unchanged by it.  Off by default;
+    fixed at construction (collision_tallies tells); combines with
+    linear=True and with currents=True.
     """
 
     def __init__(self, mesh, num_particles: int, device: str = "auto",
                  ngroups: int = 1, nscores: int = 1, linear: bool = False,
-                 currents: bool = False):
+                 currents: bool = False, collisions: bool = False):
         if linear and currents:
             raise ValueError(
                 "currents=True cannot be combined with linear=True "
                 "(not implemented)")
         self._eng = _core.Engine(mesh, num_particles, device, ngroups,
-                                 nscores, bool(linear), bool(currents))
+                                 nscores, bool(linear), bool(currents),
+                                 bool(collisions))
         self.mesh = mesh
         self.ngroups = ngroups
         self.nscores = nscores
         self.linear = bool(linear)
         self.face_currents = bool(currents)
+        self.collision_tallies = bool(collisions)
 
     @property
     def num_particles(self) -> int:
@@ -166,38 +215,11 @@ class TallyEngine:
         this engine's device -- no host staging.  For GPU-side transport
         codes."""
         def ptr(t, dtype, numel):
-            if t is None:
-                return 0
-            iface = getattr(t, "__cuda_array_interface__", None)
-            if iface is None:
-                raise TypeError("move_from_device expects CUDA tensors/arrays")
-            import math
-            n = math.prod(iface["shape"]) if iface["shape"] else 1
-            if iface["typestr"] != dtype or n != numel:
-                raise TypeError(
-                    f"expected {dtype} x{numel}, got {iface['typestr']} x{n}")
-            strides = iface.get("strides")
-            if strides is not None:
-                # C-contiguity required (None == C-contiguous per protocol)
-                itemsize = int(dtype[-1])
-                expect = []
-                acc = itemsize
-                for s in reversed(iface["shape"]):
-                    expect.append(acc)
-                    acc *= s
-                if list(strides) != list(reversed(expect)):
-                    raise TypeError("move_from_device requires contiguous tensors")
-            return iface["data"][0]
+            return _device_ptr(t, dtype, numel, "move_from_device")
 
         n = self.num_particles
-        import sys
-        if sync_torch and "torch" in sys.modules:
-            # order against torch's stream: tensors produced by torch ops
-            # (.to(device), fills) must be materialized before our kernel,
-            # which runs on the engine's own HIP stream.
-            torch = sys.modules["torch"]
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
+        if sync_torch:
+            _sync_torch()
         self._eng.move_device(
             ptr(origin, "<f8", n * 3), ptr(dest, "<f8", n * 3),
             ptr(flying, "|i1", n), ptr(weights, "<f8", n),
@@ -417,7 +439,140 @@ class TallyEngine:
                 leak_fields += [(f"{lname}_g{g}", lk[k, g]) for g in range(G)]
         if S == 1 and G == 1:
             flux_fields.append(("volume", self.mesh.volumes))
-        self.mesh.write_vtk_fields(filename, flux_fields + leak_fields)
+        self.mesh.write_vtk_fields(
+            filename, flux_fields + leak_fields + self._collision_fields())
+
+    # ---- collision-estimator tallies; collisions=True engines only ----
+
+    def _require_collisions(self, what):
+        if not self.collision_tallies:
+            raise RuntimeError(
+                f"{what}: collision tallies are off: create the engine "
+                "with collisions=true (TallyEngine(..., collisions=True))")
+
+    @staticmethod
+    def _exact(a, dtype, what):
+        # no silent conversion: a converted copy would hide a wrong dtype
+        import numpy as np
+        a = np.asarray(a)
+        if a.dtype != dtype:
+            raise TypeError(f"{what} must have dtype {np.dtype(dtype).name}, "
+                            f"got {a.dtype.name}")
+        return np.ascontiguousarray(a)
+
+    def score_collisions(self, active, weights, groups=None, responses=None):
+        """Collision estimator at the particles' committed positions: every
+        particle i with active[i] != 0 (int8, num_particles) that sits in
+        the mesh adds weights[i] (float64) -- times responses[i, k] per
+        score when responses (n x nscores) are given, else to score 0 only
+        -- to collisions()[..., e] at the element e the engine holds for
+        it, in group groups[i] % ngroups (uint16; group 0 without).  An
+        active particle that is unlocated or escaped adds nothing and
+        counts into stats()["collision_misses"]; the others into
+        stats()["collisions_scored"].  Nothing else changes: not active,
+        not the particle state, not flux()."""
+        self._require_collisions("score_collisions()")
+        import numpy as np
+        self._eng.score_collisions(
+            self._exact(active, np.int8, "active").ravel(),
+            self._exact(weights, np.float64, "weights").ravel(),
+            groups, responses)
+
+    def score_points(self, points, weights, groups=None, responses=None):
+        """Collision estimator at n free points (n x 3 float64; n is
+        independent of num_particles, n == 0 is a no-op): each point is
+        localized like copy_initial_position() does and then scores like a
+        particle in score_collisions(); a point outside the mesh is a
+        miss."""
+        self._require_collisions("score_points()")
+        import numpy as np
+        self._eng.score_points(
+            self._exact(points, np.float64, "points").ravel(),
+            self._exact(weights, np.float64, "weights").ravel(),
+            groups, responses)
+
+    def score_collisions_from_device(self, active, weights, groups=None,
+                                     responses=None, sync_torch=True):
+        """score_collisions() on GPU tensors already on this engine's device
+        (same checking and torch ordering as move_from_device); nothing is
+        staged.  GPU engines only."""
+        self._require_collisions("score_collisions_from_device()")
+        who = "score_collisions_from_device"
+        n = self.num_particles
+        ptrs = (_device_ptr(active, "|i1", n, who),
+                _device_ptr(weights, "<f8", n, who),
+                _device_ptr(groups, "<u2", n, who),
+                _device_ptr(responses, "<f8", n * self.nscores, who))
+        if sync_torch:
+            _sync_torch()
+        self._eng.score_collisions_device(*ptrs)
+
+    def score_points_from_device(self, points, weights, groups=None,
+                                 responses=None, sync_torch=True):
+        """score_points() on GPU tensors already on this engine's device:
+        points (n x 3 float64) and weights (n float64) set n.  The call is
+        queued on the engine's stream; readbacks and synchronize() wait for
+        it.  GPU engines only."""
+        self._require_collisions("score_points_from_device()")
+        who = "score_points_from_device"
+        iface = getattr(weights, "__cuda_array_interface__", None)
+        if iface is None:
+            raise TypeError(f"{who} expects CUDA tensors/arrays")
+        import math
+        n = math.prod(iface["shape"]) if iface["shape"] else 1
+        ptrs = (_device_ptr(points, "<f8", n * 3, who),
+                _device_ptr(weights, "<f8", n, who),
+                _device_ptr(groups, "<u2", n, who),
+                _device_ptr(responses, "<f8", n * self.nscores, who))
+        if sync_torch:
+            _sync_torch()
+        self._eng.score_points_device(n, *ptrs)
+
+    def collisions(self):
+        """Collision tally of the current batch, shaped like flux()."""
+        self._require_collisions("collisions()")
+        return self._eng.collisions().reshape(self._tally_shape())
+
+    def collision_sum(self):
+        """Collisions accumulated over the closed batches (end_batch() adds
+        the per-batch collisions here and zeroes them); shaped like
+        flux()."""
+        self._require_collisions("collision_sum()")
+        return self._eng.collision_sum().reshape(self._tally_shape())
+
+    def collision_sum_sq(self):
+        """Sum over the closed batches of the squared per-batch collisions;
+        shaped like flux()."""
+        self._require_collisions("collision_sum_sq()")
+        return self._eng.collision_sum_sq().reshape(self._tally_shape())
+
+    def collision_statistics(self):
+        """batch_statistics() of the collision tally: (mean, rel_std_error)
+        over the closed batches, shaped like flux()."""
+        self._require_collisions("collision_statistics()")
+        mean, rel = self._mean_rel(self._eng.collision_sum(),
+                                   self._eng.collision_sum_sq())
+        return (mean.reshape(self._tally_shape()),
+                rel.reshape(self._tally_shape()))
+
+    def _collision_fields(self):
+        """Cell fields of write_tally_results for the collision tally: named
+        like the flux fields with the stem "collisions", each divided by the
+        element volume.  Empty without collision tallies."""
+        if not self.collision_tallies:
+            return []
+        S, G, ne = self.nscores, self.ngroups, self.mesh.nelems
+        c = self.collisions().reshape(S, G, ne)
+        fields = []
+        for k in range(S):
+            name = "collisions" if k == 0 else f"collisions_score{k}"
+            fields.append(
+                (name, _core.normalize_flux(self.mesh, c[k].sum(axis=0))))
+            if G > 1:
+                fields += [(f"{name}_g{g}",
+                            _core.normalize_flux(self.mesh, c[k, g]))
+                           for g in range(G)]
+        return fields
 
     def elem_ids(self):
         return self._eng.elem_ids()
@@ -444,22 +599,27 @@ class TallyEngine:
         statistics; the reference has no variance accounting)."""
         self._eng.end_batch()
 
-    def batch_statistics(self):
-        """Returns (mean, rel_std_error) over the closed batches, shaped
-        like flux().  rel_std_error = sigma_of_mean / |mean| (0 where
-        mean == 0)."""
+    def _mean_rel(self, s1, s2):
+        """(mean, rel_std_error) of a tally from its batch sum and sum of
+        squares (flat arrays)."""
         import numpy as np
 
         nb = self._eng.num_batches
         if nb < 1:
             raise RuntimeError("no batches closed yet (call end_batch)")
-        s1 = self._eng.batch_sum()
-        s2 = self._eng.batch_sum_sq()
         mean = s1 / nb
         var = np.maximum(s2 / nb - mean * mean, 0.0)
         sem = np.sqrt(var / max(nb - 1, 1))
         rel = np.divide(sem, np.abs(mean), out=np.zeros_like(sem),
                         where=mean != 0)
+        return mean, rel
+
+    def batch_statistics(self):
+        """Returns (mean, rel_std_error) over the closed batches, shaped
+        like flux().  rel_std_error = sigma_of_mean / |mean| (0 where
+        mean == 0)."""
+        mean, rel = self._mean_rel(self._eng.batch_sum(),
+                                   self._eng.batch_sum_sq())
         if self.nscores > 1 and self.ngroups > 1:
             shape = (self.nscores, self.ngroups, self.mesh.nelems)
         elif self.nscores > 1:
@@ -482,6 +642,9 @@ class TallyEngine:
         # ... and face-current engines a "currents" key
         if self.face_currents:
             extra["currents"] = self.currents()
+        # ... and collision-tally engines a "collisions" key
+        if self.collision_tallies:
+            extra["collisions"] = self.collisions()
         np.savez_compressed(
             path,
             flux=self.flux(),
@@ -507,6 +670,10 @@ class TallyEngine:
         if self.face_currents and "currents" in d.files:
             self._eng.set_currents(
                 np.ascontiguousarray(d["currents"], dtype=np.float64).ravel())
+        if self.collision_tallies and "collisions" in d.files:
+            self._eng.set_collisions(
+                np.ascontiguousarray(d["collisions"],
+                                     dtype=np.float64).ravel())
         self._eng.set_particle_state(
             np.ascontiguousarray(d["positions"], dtype=np.float64).ravel(),
             np.ascontiguousarray(d["elem_ids"], dtype=np.int32),
@@ -532,10 +699,16 @@ class TallyEngine:
         Face-current engines additionally write one cell field "leakage"
         per flux field (same name suffixes: leakage, leakage_g0, score1 ->
         leakage_score1, ...): the element's currents summed over its vacuum
-        boundary faces, not normalized."""
+        boundary faces, not normalized.
+        Collision-tally engines additionally write, after everything else,
+        one cell field "collisions" per flux field (collisions,
+        collisions_g0, collisions_score1, ...): collisions() divided by the
+        element volume.  Engines without these options write exactly the
+        reference's file."""
         if self.face_currents:
             self._write_with_leakage(filename)
             return
+        coll = self._collision_fields()
         points = []
         if self.linear:
             m0 = self.moments().reshape(self.nscores, self.ngroups,
@@ -555,7 +728,7 @@ class TallyEngine:
                     fields += [(f"{name}_g{g}",
                                 _core.normalize_flux(self.mesh, f[k, g]))
                                for g in range(self.ngroups)]
-            self.mesh.write_vtk_fields(filename, fields, points)
+            self.mesh.write_vtk_fields(filename, fields + coll, points)
             return
         if self.ngroups > 1:
             # one normalized field per energy group + the total
@@ -563,14 +736,14 @@ class TallyEngine:
             fields = [("flux", _core.normalize_flux(self.mesh, f.sum(axis=0)))]
             fields += [(f"flux_g{g}", _core.normalize_flux(self.mesh, f[g]))
                        for g in range(self.ngroups)]
-            self.mesh.write_vtk_fields(filename, fields, points)
+            self.mesh.write_vtk_fields(filename, fields + coll, points)
             return
-        if points:
+        if points or coll:
             # same two cell fields write_tally_vtk writes
             self.mesh.write_vtk_fields(
                 filename,
                 [("flux", _core.normalize_flux(self.mesh, self._eng.flux())),
-                 ("volume", self.mesh.volumes)], points)
+                 ("volume", self.mesh.volumes)] + coll, points)
             return
         _core.write_tally_vtk(filename, self.mesh, self._eng.flux())
 
