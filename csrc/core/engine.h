@@ -65,6 +65,13 @@ struct EngineStats {
   // are not in the mesh (unlocated or escaped).  Cumulative.
   int64_t collisions_scored = 0;
   int64_t collision_misses = 0;
+  // Stateless track tallies (Engine::tally_tracks): tracks handed over (the
+  // sum of n over calls), times a track entered the mesh from outside
+  // through a boundary face (a start inside the mesh is not an entry), and
+  // tallied tracks that were never inside the mesh.  Cumulative.
+  int64_t tracks = 0;
+  int64_t track_entries = 0;
+  int64_t track_misses = 0;
 };
 
 // First-K lost-particle capture (walks that hit max_steps): enough to find
@@ -178,6 +185,38 @@ public:
     (void)d_responses; (void)d_out_dest; (void)d_in_t; (void)d_in_prev;
     (void)d_out_o; (void)d_out_t; (void)d_out_prev;
     throw std::runtime_error("walk_raw_device requires the GPU engine");
+  }
+
+  // Stateless track tallies: n free segments origin -> dest with weights
+  // (any n, independent of num_particles; n == 0 is a no-op) that may start
+  // or end anywhere, pass through the mesh from outside, leave through a
+  // hole and come back, or miss it (track.h has the rules of one track).
+  // Each track is independent; the call never reads or writes particle
+  // state (positions, elements, escaped flags, the origin-elision cache).
+  // Contributions go where move()'s go: the flux, on linear engines the
+  // moments too, on currents engines the currents too (no re-exit rule, as
+  // in walk_raw); groups and responses as in move().  The collision tally is
+  // not touched.  A zero-length or zero-weight track is skipped before any
+  // geometry.  Counted in EngineStats::tracks / track_entries /
+  // track_misses; a track that runs out of steps or entries counts into
+  // lost_particles, its lost_records row carrying the track index.
+  // Synchronous; host memory.  Throws std::invalid_argument on a mesh with
+  // partition-cut faces (nbr < -1).
+  virtual void tally_tracks(int64_t n, const double *origin,
+                            const double *dest, const double *weights,
+                            const uint16_t *groups = nullptr,
+                            const double *responses = nullptr) = 0;
+  // Device-resident twin: every array already lives in this engine's device
+  // memory; queued on the engine's compute stream, nothing is staged.
+  // Throws on the CPU engine.
+  virtual void tally_tracks_device(int64_t n, const double *d_origin,
+                                   const double *d_dest,
+                                   const double *d_weights,
+                                   const uint16_t *d_groups = nullptr,
+                                   const double *d_responses = nullptr) {
+    (void)n; (void)d_origin; (void)d_dest; (void)d_weights; (void)d_groups;
+    (void)d_responses;
+    throw std::runtime_error("tally_tracks_device requires the GPU engine");
   }
 
   // Read back state (host copies).

@@ -2,6 +2,7 @@
 // no-GPU plumbing path (BASELINE config 1).
 #include "engine.h"
 #include "tally_sink.h"
+#include "track.h"
 #include "walk.h"
 
 #include <atomic>
@@ -38,6 +39,7 @@ class CpuEngine final : public Engine {
   };
   struct Counts {
     int64_t lost = 0, reloc = 0;
+    int64_t entries = 0, misses = 0; // tally_tracks only
   };
 
 public:
@@ -282,6 +284,68 @@ public:
     }
   }
 
+  // Stateless track tallies (engine.h, track.h).  Threads like walk_raw;
+  // particle state is never looked at.
+  void tally_tracks(int64_t n, const double *origin, const double *dest,
+                    const double *weights, const uint16_t *groups = nullptr,
+                    const double *responses = nullptr) override {
+    if (n <= 0) return;
+    if (tracks_refused_)
+      throw std::invalid_argument(
+          "track tallies do not support a mesh with partition-cut faces");
+    if (mesh_.face_cell_start.empty()) {
+      try {
+        mesh_.build_face_grid();
+      } catch (const std::invalid_argument &) {
+        tracks_refused_ = true; // checked once, the answer is kept
+        throw;
+      }
+    }
+    const LocGrid &g = mesh_.grid;
+    const TallyMesh tm = tally_mesh();
+    const TrackMesh trk{
+        tm.planes,
+        mesh_.planes32.data(),
+        tm.nbr,
+        GridView{g.nx, g.ny, g.nz, g.lo, g.inv_h, g.cell_start.data(),
+                 g.cell_tets.data()},
+        FaceGridView{g.nx, g.ny, g.nz, g.lo, g.inv_h,
+                     mesh_.face_cell_start.data(),
+                     mesh_.face_cell_faces.data()},
+        tm.face_bc,
+        tm.pidx,
+        mesh_.periodic_elem.data(),
+        mesh_.periodic_shift.data(),
+        reflective,
+        loc_tol_,
+        max_steps > 0 ? max_steps : default_max_steps(mesh_)};
+    const Counts c = for_each_particle(
+        n, std::thread::hardware_concurrency(),
+        [&](int64_t i, const Tallies &out, Counts &k) {
+          const Vec3 o{origin[i * 3], origin[i * 3 + 1], origin[i * 3 + 2]};
+          const Vec3 d{dest[i * 3], dest[i * 3 + 1], dest[i * 3 + 2]};
+          TrackResult r;
+          tally_walk</*ReexitRule=*/false>(
+              out, groups, responses, i, tm, false, [&](auto &sink) {
+                if (walk_fp32)
+                  track_tally<true>(trk, o, d, weights[i], sink, r);
+                else
+                  track_tally<false>(trk, o, d, weights[i], sink, r);
+              });
+          k.entries += r.entries;
+          k.misses += r.miss;
+          if (r.loose) loose_++;
+          if (r.lost) {
+            k.lost++;
+            record_lost(i, r.lost_pos);
+          }
+        });
+    stats_.tracks += n;
+    stats_.track_entries += c.entries;
+    stats_.track_misses += c.misses;
+    stats_.lost_particles += c.lost;
+  }
+
   // Collision-estimator scoring (engine.h).  One gather and one add per
   // particle; a serial loop, so the sums are in caller order.
   void score_collisions(const int8_t *active, const double *weights,
@@ -511,6 +575,8 @@ private:
     for (const Counts &c : counts) {
       total.lost += c.lost;
       total.reloc += c.reloc;
+      total.entries += c.entries;
+      total.misses += c.misses;
     }
     return total;
   }
@@ -574,6 +640,7 @@ private:
   // collision tallies only, else empty; never a for_each_particle target
   std::vector<double> collisions_, collision_sum_, collision_sq_;
   int64_t nbatches_ = 0;
+  bool tracks_refused_ = false; // tally_tracks: the mesh has cut faces
   std::vector<int32_t> elem_;
   std::vector<uint8_t> escaped_;
   mutable EngineStats stats_;

@@ -1,4 +1,5 @@
 #include "mesh.h"
+#include "track.h"
 
 #include <algorithm>
 #include <cmath>
@@ -96,6 +97,70 @@ void Mesh::build_inv_heights() {
   inv_heights.resize((size_t)nelems * 4);
   for (int64_t i = 0; i < nelems * 4; ++i)
     inv_heights[i] = 1.0 / plane_eval(planes[i], vert(tet2vert[i]));
+}
+
+void Mesh::build_face_grid() {
+  if (nbr.size() != (size_t)nelems * 4 || grid.cell_start.empty())
+    throw std::runtime_error("build_face_grid: call finalize() first");
+  if (nelems >= ((int64_t)1 << 29))
+    throw std::invalid_argument(
+        "build_face_grid: flat face indices do not fit an int32");
+  for (int32_t nb : nbr)
+    if (nb < -1)
+      throw std::invalid_argument(
+          "track tallies do not support a mesh with partition-cut faces "
+          "(a submesh from extract_submesh)");
+  const int64_t ncells = (int64_t)grid.nx * grid.ny * grid.nz;
+  // cell range of face fidx's padded AABB
+  auto cell_range = [&](int64_t fidx, int lo[3], int hi[3]) {
+    double blo[3] = {1e300, 1e300, 1e300}, bhi[3] = {-1e300, -1e300, -1e300};
+    for (int k = 0; k < 3; ++k) {
+      const Vec3 p = vert(tet2vert[(fidx >> 2) * 4 + kFaceVerts[fidx & 3][k]]);
+      const double u[3] = {(p.x - grid.lo.x) * grid.inv_h.x,
+                           (p.y - grid.lo.y) * grid.inv_h.y,
+                           (p.z - grid.lo.z) * grid.inv_h.z};
+      for (int a = 0; a < 3; ++a) {
+        blo[a] = std::min(blo[a], u[a]);
+        bhi[a] = std::max(bhi[a], u[a]);
+      }
+    }
+    const int n[3] = {grid.nx, grid.ny, grid.nz};
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = ray_cell(blo[a] - kFaceGridPad, n[a]);
+      hi[a] = ray_cell(bhi[a] + kFaceGridPad, n[a]);
+    }
+  };
+  auto is_vacuum_face = [&](int64_t fidx) {
+    return nbr[fidx] == -1 &&
+           !(!periodic_idx.empty() && periodic_idx[fidx] >= 0) &&
+           !face_is_reflective(fidx);
+  };
+  // two passes over the faces in ascending flat index: count, then fill, so
+  // every cell's list is ascending too
+  face_cell_start.assign(ncells + 1, 0);
+  for (int pass = 0; pass < 2; ++pass) {
+    std::vector<int32_t> cursor;
+    if (pass == 1) {
+      for (int64_t c = 0; c < ncells; ++c)
+        face_cell_start[c + 1] += face_cell_start[c];
+      face_cell_faces.assign(face_cell_start[ncells], 0);
+      cursor.assign(face_cell_start.begin(), face_cell_start.end() - 1);
+    }
+    for (int64_t fidx = 0; fidx < nelems * 4; ++fidx) {
+      if (!is_vacuum_face(fidx)) continue;
+      int lo[3], hi[3];
+      cell_range(fidx, lo, hi);
+      for (int cz = lo[2]; cz <= hi[2]; ++cz)
+        for (int cy = lo[1]; cy <= hi[1]; ++cy)
+          for (int cx = lo[0]; cx <= hi[0]; ++cx) {
+            const int64_t c = ((int64_t)cz * grid.ny + cy) * grid.nx + cx;
+            if (pass == 0)
+              face_cell_start[c + 1]++;
+            else
+              face_cell_faces[cursor[c]++] = (int32_t)fidx;
+          }
+    }
+  }
 }
 
 std::vector<int64_t> Mesh::face_twins() const {

@@ -96,6 +96,18 @@ struct Mesh {
   std::vector<double> inv_heights;
   void build_inv_heights();
 
+  // Boundary-face grid for the entry search of the stateless track tallies
+  // (track.h ray_enter): over the cells of `grid`, CSR lists of the vacuum
+  // boundary faces (flat index elem*4+f; nbr == -1, neither periodic nor
+  // per-face reflective) whose triangle AABB, inflated by kFaceGridPad of a
+  // cell, overlaps the cell.  NOT built by finalize(): only engines that
+  // tally free tracks need it and call build_face_grid() on their own mesh
+  // copy, once.  Throws std::invalid_argument on a mesh with partition-cut
+  // faces (nbr < -1) or too many faces for an int32 flat index.
+  std::vector<int32_t> face_cell_start; // ncells+1; empty = not built
+  std::vector<int32_t> face_cell_faces; // CSR payload
+  void build_face_grid();
+
   // nelems*4: flat index (elem*4+f) of the same face seen from the
   // neighbor; for a periodic face the paired face; -1 for every other
   // boundary face and for a partition-cut face (nbr < -1).

@@ -33,6 +33,7 @@
 #include "../core/engine.h"
 #include "../core/origin_delta.h"
 #include "../core/tally_sink.h"
+#include "../core/track.h"
 #include "../core/walk.h"
 #include "hip_util.h"
 
@@ -734,6 +735,81 @@ __global__ void k_walk_raw(const Plane *__restrict__ planes,
   }
 }
 
+// Sum over the wave's lanes of a small non-negative per-lane count, by bit
+// planes: one ballot and one popcount per bit any lane has set.  Executed by
+// all 64 lanes; every lane gets the sum.
+__device__ __forceinline__ unsigned long long wave_count_sum(unsigned v) {
+  unsigned long long sum = 0;
+  for (int b = 0; __ballot(v >> b) != 0ull; ++b)
+    sum += (unsigned long long)__popcll(__ballot((v >> b) & 1u)) << b;
+  return sum;
+}
+
+// Engine::tally_tracks on the device: one lane per free track, in caller
+// order, k_walk_raw's XCD-aware block->range remap.  Each track is
+// core/track.h track_tally -- localize the origin, walk, and on every vacuum
+// clip search the boundary-face grid for the next entry -- through the tally
+// sink with plain atomics into flux slice 0 (responses a run-time choice, no
+// re-exit rule), as k_walk_raw.  Reads no particle state.  The loop's trip
+// count is wave-uniform, so entries and misses are summed per wave and
+// flushed with one atomicAdd each: counts[0] += entries, counts[1] += misses.
+template <bool F32, TallyMode Mode>
+__global__ void k_tally_tracks(TrackMesh trk, const double *__restrict__ origin,
+                               const double *__restrict__ dest,
+                               const double *__restrict__ weights,
+                               const uint16_t *__restrict__ groups,
+                               const double *__restrict__ resp,
+                               double *__restrict__ flux,
+                               double *__restrict__ companion,
+                               const double *__restrict__ inv_h,
+                               unsigned long long *__restrict__ counts,
+                               unsigned long long *__restrict__ lost,
+                               double *__restrict__ lostrec,
+                               unsigned long long *__restrict__ loose,
+                               int64_t n, int ngroups, int64_t nelems,
+                               int nscores) {
+  const TallyMesh tmesh{trk.planes, inv_h,    trk.nbr,
+                        trk.face_bc, trk.pidx, trk.reflective};
+  const unsigned bpx = gridDim.x / 8u;
+  const unsigned vb = bpx ? (blockIdx.x % 8u) * bpx + blockIdx.x / 8u
+                          : blockIdx.x;
+  const int64_t per_blk = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t base = (int64_t)vb * per_blk;
+  const int64_t end = base + per_blk < n ? base + per_blk : n;
+  const int lane = (int)(threadIdx.x & 63u);
+  unsigned long long entries = 0, misses = 0;
+  // i0 is the wave's first track of the pass: the same in all 64 lanes
+  for (int64_t i0 = base + (threadIdx.x - lane); i0 < end; i0 += blockDim.x) {
+    const int64_t i = i0 + lane;
+    TrackResult r;
+    if (i < end) {
+      const Vec3 o{origin[i * 3], origin[i * 3 + 1], origin[i * 3 + 2]};
+      const Vec3 d{dest[i * 3], dest[i * 3 + 1], dest[i * 3 + 2]};
+      TallySink<Mode, /*Scored=*/true, AtomicAdder> sink{
+          AtomicAdder{}, flux, companion,
+          tally_group_offset(groups, i, ngroups, nelems),
+          (int64_t)ngroups * nelems, resp, i, nscores, tmesh, false};
+      track_tally<F32>(trk, o, d, weights[i], sink, r);
+      if (r.loose) atomicAdd(loose, 1ull); // rare by construction
+      if (r.lost) {
+        const unsigned long long k = atomicAdd(lost, 1ull);
+        if (k < (unsigned long long)kMaxLostRecords) {
+          lostrec[k * 4] = (double)i;
+          lostrec[k * 4 + 1] = r.lost_pos.x;
+          lostrec[k * 4 + 2] = r.lost_pos.y;
+          lostrec[k * 4 + 3] = r.lost_pos.z;
+        }
+      }
+    }
+    entries += wave_count_sum((unsigned)r.entries);
+    misses += (unsigned long long)__popcll(__ballot(r.miss));
+  }
+  if (lane == 0) {
+    if (entries) atomicAdd(&counts[0], entries);
+    if (misses) atomicAdd(&counts[1], misses);
+  }
+}
+
 // Tally slices: S independent copies of the flux array, selected by
 // blockIdx & (S-1), reduced at readout.  The hot-element (point-source)
 // mitigation: measured on MI355X (profiles/README.md round 2), the
@@ -1130,6 +1206,118 @@ public:
     PT_HIP_CHECK(hipGetLastError());
   }
 
+  // Grow-once scratch of tally_tracks, like ScorePointsScratch.
+  // Every array has a pinned host twin the caller's rows are copied into
+  // first, so the uploads run async at the full link rate whatever memory
+  // the caller passed.
+  struct TrackScratch {
+    DeviceBuffer<double> origin, dest, w, resp;
+    DeviceBuffer<uint16_t> groups;
+    PinnedBuffer<double> h_origin, h_dest, h_w, h_resp;
+    PinnedBuffer<uint16_t> h_groups;
+  };
+
+  // Upload `count` elements of src through the pinned twin, on s_comp_.
+  template <class T>
+  void stage_pinned(const T *src, int64_t count, PinnedBuffer<T> &pin,
+                    DeviceBuffer<T> &dev) {
+    if (pin.size() < count) pin.allocate(count + count / 4);
+    dev.reserve(count);
+    std::memcpy(pin.get(), src, (size_t)count * sizeof(T));
+    stage(pin.get(), (size_t)count * sizeof(T), dev, s_comp_);
+  }
+
+  // Stateless track tallies (engine.h, core/track.h).  The uploads and the
+  // kernel are queued on the compute stream, behind every queued move, and
+  // the call returns once they have drained, so the scratch is free for the
+  // next call.
+  void tally_tracks(int64_t n, const double *origin, const double *dest,
+                    const double *weights, const uint16_t *groups = nullptr,
+                    const double *responses = nullptr) override {
+    if (n <= 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    ensure_face_grid();
+    stage_pinned(origin, n * 3, tt_.h_origin, tt_.origin);
+    stage_pinned(dest, n * 3, tt_.h_dest, tt_.dest);
+    stage_pinned(weights, n, tt_.h_w, tt_.w);
+    if (groups) stage_pinned(groups, n, tt_.h_groups, tt_.groups);
+    if (responses)
+      stage_pinned(responses, n * nscores, tt_.h_resp, tt_.resp);
+    launch_tally_tracks(n, tt_.origin, tt_.dest, tt_.w,
+                        groups ? tt_.groups.get() : nullptr,
+                        responses ? tt_.resp.get() : nullptr);
+    PT_HIP_CHECK(hipStreamSynchronize(s_comp_));
+  }
+
+  void tally_tracks_device(int64_t n, const double *d_origin,
+                           const double *d_dest, const double *d_weights,
+                           const uint16_t *d_groups = nullptr,
+                           const double *d_responses = nullptr) override {
+    if (n <= 0) return;
+    PT_HIP_CHECK(hipSetDevice(device_));
+    ensure_face_grid();
+    launch_tally_tracks(n, d_origin, d_dest, d_weights, d_groups, d_responses);
+  }
+
+  // First tally_tracks call: build the boundary-face grid on the engine's
+  // mesh copy (throws on a mesh with partition-cut faces, every time: a
+  // refused mesh is remembered) and upload it, once.
+  void ensure_face_grid() {
+    if (d_track_counts_) return;
+    if (tracks_refused_)
+      throw std::invalid_argument(
+          "track tallies do not support a mesh with partition-cut faces");
+    try {
+      mesh_.build_face_grid();
+    } catch (const std::invalid_argument &) {
+      tracks_refused_ = true; // checked once, the answer is kept
+      throw;
+    }
+    d_face_start_ = upload(mesh_.face_cell_start);
+    d_face_list_.allocate((int64_t)mesh_.face_cell_faces.size() + 1);
+    PT_HIP_CHECK(hipMemcpy(d_face_list_, mesh_.face_cell_faces.data(),
+                           mesh_.face_cell_faces.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice));
+    d_track_counts_.allocate(2);
+    PT_HIP_CHECK(
+        hipMemset(d_track_counts_, 0, 2 * sizeof(unsigned long long)));
+  }
+
+  void launch_tally_tracks(int64_t n, const double *origin, const double *dest,
+                           const double *weights, const uint16_t *groups,
+                           const double *resp) {
+    const TrackMesh trk{
+        d_planes_,
+        d_planes32_,
+        d_nbr_,
+        grid_view_,
+        FaceGridView{grid_view_.nx, grid_view_.ny, grid_view_.nz,
+                     grid_view_.lo, grid_view_.inv_h, d_face_start_,
+                     d_face_list_},
+        d_face_bc_,
+        d_pidx_,
+        d_pelem_,
+        d_pshift_,
+        reflective,
+        loc_tol_,
+        max_steps > 0 ? max_steps : default_max_steps(mesh_)};
+    using M = TallyMode;
+    const auto kernel =
+        linear ? (walk_fp32 ? k_tally_tracks<true, M::Linear>
+                            : k_tally_tracks<false, M::Linear>)
+        : face_currents
+            ? (walk_fp32 ? k_tally_tracks<true, M::Currents>
+                         : k_tally_tracks<false, M::Currents>)
+            : (walk_fp32 ? k_tally_tracks<true, M::Flux>
+                         : k_tally_tracks<false, M::Flux>);
+    kernel<<<grid_blocks(n), kBlock, 0, s_comp_>>>(
+        trk, origin, dest, weights, groups, resp, d_flux_,
+        linear ? d_moments_.get() : d_cur_.get(), d_inv_h_, d_track_counts_,
+        d_lost_, d_lostrec_, d_loose_, n, ngroups, mesh_.nelems, nscores);
+    PT_HIP_CHECK(hipGetLastError());
+    stats_.tracks += n;
+  }
+
   // Persistent scratch for walk_raw.  The partitioned driver calls
   // walk_raw once per exchange round; per-call hipMalloc/hipFree pairs
   // would device-sync every round, so the buffers are grown once and
@@ -1410,6 +1598,13 @@ public:
           hipMemcpy(c, d_coll_counts_, sizeof c, hipMemcpyDeviceToHost));
       stats_.collisions_scored = (int64_t)c[0];
       stats_.collision_misses = (int64_t)c[1];
+    }
+    if (d_track_counts_) {
+      unsigned long long c[2] = {0, 0};
+      PT_HIP_CHECK(
+          hipMemcpy(c, d_track_counts_, sizeof c, hipMemcpyDeviceToHost));
+      stats_.track_entries = (int64_t)c[0];
+      stats_.track_misses = (int64_t)c[1];
     }
     return stats_;
   }
@@ -1848,6 +2043,13 @@ private:
   DeviceBuffer<int32_t> d_pidx_, d_pelem_;
   DeviceBuffer<double> d_pshift_;
   WalkRawScratch wr_;
+  // Track tallies only, all from the first tally_tracks call: the
+  // boundary-face grid (CSR over grid_view_'s cells), the {entries, misses}
+  // counters and the host path's scratch.
+  DeviceBuffer<int32_t> d_face_start_, d_face_list_;
+  DeviceBuffer<unsigned long long> d_track_counts_;
+  bool tracks_refused_ = false;
+  TrackScratch tt_;
   int64_t nbatches_ = 0;
 
   DeviceBuffer<uint64_t> d_keys_, d_keys2_;

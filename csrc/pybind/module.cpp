@@ -1080,6 +1080,42 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("n"), py::arg("points_ptr"), py::arg("weights_ptr"),
            py::arg("groups_ptr") = 0, py::arg("responses_ptr") = 0)
+      // stateless track tallies (engine.h): n free segments, n set by weights
+      .def("tally_tracks",
+           [](PyEngine &e, py::array_t<double, py::array::c_style> origins,
+              py::array_t<double, py::array::c_style> dests,
+              py::array_t<double, py::array::c_style> weights,
+              py::object groups, py::object responses) {
+             const int64_t n = (int64_t)weights.size();
+             if ((int64_t)origins.size() != n * 3 ||
+                 (int64_t)dests.size() != n * 3)
+               throw std::runtime_error(
+                   "tally_tracks: origins and dests must have size 3*n");
+             GroupsArray garr;
+             DoubleArray rarr;
+             const uint16_t *gp =
+                 optional_groups(groups, garr, n, "tally_tracks");
+             const double *rp = optional_responses(
+                 responses, rarr, n, e.eng->nscores, "tally_tracks");
+             py::gil_scoped_release nogil;
+             e.eng->tally_tracks(n, origins.data(), dests.data(),
+                                 weights.data(), gp, rp);
+           },
+           py::arg("origins"), py::arg("dests"), py::arg("weights"),
+           py::arg("groups") = py::none(), py::arg("responses") = py::none())
+      .def("tally_tracks_device",
+           [](PyEngine &e, int64_t n, uintptr_t origins_ptr,
+              uintptr_t dests_ptr, uintptr_t weights_ptr, uintptr_t groups_ptr,
+              uintptr_t responses_ptr) {
+             py::gil_scoped_release nogil;
+             e.eng->tally_tracks_device(
+                 n, (const double *)origins_ptr, (const double *)dests_ptr,
+                 (const double *)weights_ptr, (const uint16_t *)groups_ptr,
+                 (const double *)responses_ptr);
+           },
+           py::arg("n"), py::arg("origins_ptr"), py::arg("dests_ptr"),
+           py::arg("weights_ptr"), py::arg("groups_ptr") = 0,
+           py::arg("responses_ptr") = 0)
       .def("collisions", [](const PyEngine &e) { return vec_to_np(e.eng->collisions()); })
       .def("collision_sum", [](const PyEngine &e) { return vec_to_np(e.eng->collision_sum()); })
       .def("collision_sum_sq", [](const PyEngine &e) { return vec_to_np(e.eng->collision_sum_sq()); })
@@ -1114,6 +1150,9 @@ PYBIND11_MODULE(_core, m) {
         d["origin_pass_seconds"] = s.origin_pass_seconds;
         d["collisions_scored"] = s.collisions_scored;
         d["collision_misses"] = s.collision_misses;
+        d["tracks"] = s.tracks;
+        d["track_entries"] = s.track_entries;
+        d["track_misses"] = s.track_misses;
         return d;
       })
       // First-K lost-walk capture: (k, 4) array of

@@ -242,6 +242,49 @@ class TallyEngine:
         return self._eng.walk_raw(pos, dest, elem, weights, groups,
                                   responses, in_t, in_prev, resume)
 
+    def tally_tracks(self, origins, dests, weights, groups=None,
+                     responses=None):
+        """Stateless track tallies: n free segments origins[i] -> dests[i]
+        (n x 3 float64 each) with weights (n float64); n is independent of
+        num_particles and n == 0 is a no-op.  A track may start or end
+        anywhere: it is tallied wherever it runs inside the mesh, entering
+        through vacuum boundary faces as often as it takes (a hole, a notch,
+        a mesh that covers part of the geometry), and a track that never
+        meets the mesh counts as a miss.  Contributions land where move()'s
+        do -- flux(), and moments() / currents() on engines that have them
+        -- with groups and responses applied as in move(); particle state
+        and the collision tally are never touched.  stats() counts
+        "tracks", "track_entries" (entries from outside through a boundary
+        face; a start inside is none) and "track_misses".  Raises ValueError
+        on a mesh with partition-cut faces."""
+        import numpy as np
+        self._eng.tally_tracks(
+            self._exact(origins, np.float64, "origins").ravel(),
+            self._exact(dests, np.float64, "dests").ravel(),
+            self._exact(weights, np.float64, "weights").ravel(),
+            groups, responses)
+
+    def tally_tracks_from_device(self, origins, dests, weights, groups=None,
+                                 responses=None, sync_torch=True):
+        """tally_tracks() on GPU tensors already on this engine's device:
+        origins, dests (n x 3 float64) and weights (n float64) set n.  The
+        call is queued on the engine's stream; readbacks and synchronize()
+        wait for it.  GPU engines only."""
+        who = "tally_tracks_from_device"
+        iface = getattr(weights, "__cuda_array_interface__", None)
+        if iface is None:
+            raise TypeError(f"{who} expects CUDA tensors/arrays")
+        import math
+        n = math.prod(iface["shape"]) if iface["shape"] else 1
+        ptrs = (_device_ptr(origins, "<f8", n * 3, who),
+                _device_ptr(dests, "<f8", n * 3, who),
+                _device_ptr(weights, "<f8", n, who),
+                _device_ptr(groups, "<u2", n, who),
+                _device_ptr(responses, "<f8", n * self.nscores, who))
+        if sync_torch:
+            _sync_torch()
+        self._eng.tally_tracks_device(n, *ptrs)
+
     def synchronize(self):
         self._eng.synchronize()
 

@@ -42,6 +42,7 @@ HEADERS = [
     "csrc/core/mesh.h",
     "csrc/core/walk.h",
     "csrc/core/tally_sink.h",
+    "csrc/core/track.h",
     "csrc/core/engine.h",
     "csrc/core/origin_delta.h",
     "csrc/comm/comm.h",
