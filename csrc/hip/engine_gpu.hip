@@ -540,11 +540,14 @@ __global__ void k_move(const Plane *__restrict__ planes,
                        bool cur_keyed = false) {
   static_assert(!(Linear && Currents), "linear + currents is not built");
   // Scored=false, Periodic=false is the headline instantiation:
-  // resp/nscores/pidx are unused, the slice stride stays nelems*ngroups,
-  // and the walk compiles without the score loop or the periodic branch --
-  // codegen identical to before those features existed.
+  // resp/pidx are unused and the walk compiles without the score loop or
+  // the periodic branch.  The slice stride is the allocated one in every
+  // instantiation -- nelems*ngroups*nscores, the host's fsz_, which
+  // k_reduce_slices reduces with: an engine built with nscores > 1 runs the
+  // unscored kernels whenever a move passes no responses, and its slices
+  // are still nscores scores apart.
   flux += (int64_t)(blockIdx.x & (unsigned)slice_mask) * nelems * ngroups *
-          (Scored ? nscores : 1);
+          nscores;
   constexpr TallyMode Mode = kernel_tally_mode<Linear, Currents>;
   const TallyMesh tmesh{planes, inv_h, nbr, face_bc, pidx, reflective};
   const unsigned bpx = gridDim.x / 8u;

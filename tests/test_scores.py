@@ -196,6 +196,50 @@ def test_scored_move_gpu_matches_cpu():
 
 
 @pytest.mark.gpu
+def test_scored_null_responses_is_plain_flux_gpu():
+    """GPU twin of test_scored_null_responses_is_plain_flux: a move without
+    responses on an nscores=2 engine books score 0 only, whichever flux
+    slice a block tallies into; a scored move on the same engine then lands
+    in both scores.  n = 5000 runs more than one block, hence more than one
+    slice.  Integer weights and responses."""
+    m = pt.build_box(4, 4, 4)
+    n, S = 5000, 2
+    rng = np.random.default_rng(77)
+    o = rng.uniform(0.02, 0.98, size=(n, 3))
+    d = rng.uniform(0.02, 0.98, size=(n, 3))
+    d2 = rng.uniform(0.02, 0.98, size=(n, 3))
+    w = rng.integers(1, 5, n).astype(np.float64)
+    resp = rng.integers(1, 4, size=(n, S)).astype(np.float64)
+    fly = np.ones(n, np.int8)
+
+    def bound(ref):
+        return 1e-10 * max(1.0, np.abs(ref).max())
+
+    engines = [pt.TallyEngine(m, n, device=dev, nscores=S)
+               for dev in ("cpu", "cuda:0")]
+    assert engines[1].is_gpu
+    for eng in engines:
+        eng.copy_initial_position(o.ravel())
+        eng.move(o.ravel(), d.ravel(), fly, w)
+        eng.synchronize()
+    cf, gf = (np.asarray(e.flux()).copy() for e in engines)
+    assert cf[0].any() and not cf[1].any()
+    print(f"null responses: max |score 1| {np.abs(gf[1]).max():.3e}, "
+          f"max |score 0 diff| {np.abs(gf[0] - cf[0]).max():.3e}")
+    assert not gf[1].any(), np.abs(gf[1]).max()
+    assert np.abs(gf[0] - cf[0]).max() < bound(cf[0])
+
+    for eng in engines:
+        eng.move(d.ravel(), d2.ravel(), fly, w, responses=resp)
+        eng.synchronize()
+    cf, gf = (np.asarray(e.flux()).copy() for e in engines)
+    assert cf[1].any()
+    err = np.abs(gf - cf).max()
+    print(f"then scored: max |flux diff| {err:.3e} (bound {bound(cf):.3e})")
+    assert err < bound(cf)
+
+
+@pytest.mark.gpu
 def test_scored_walk_raw_gpu():
     m = pt.build_box(5, 5, 5)
     n, S = 4000, 2

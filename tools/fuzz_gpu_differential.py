@@ -54,6 +54,9 @@ def one_trial(rng, trial):
     w = rng.uniform(0.0, 2.0, n)
     g = rng.integers(0, G, n).astype(np.uint16) if G > 1 else None
     r = rng.uniform(0.0, 2.0, (n, S)) if S > 1 else None
+    # one scored engine in five moves without responses: score 0 only
+    if S > 1 and rng.random() < 0.2:
+        r = None
     fly = np.ones(n, np.int8)
 
     ref = pt.TallyEngine(m, n, device="cpu", ngroups=G, nscores=S)
